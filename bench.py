@@ -32,6 +32,13 @@ read, include/click/sync.hh:384) and the per-output offsets all-gathered
 (dist.output_offsets); both are checked.
 
 rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run does only what that line's headline needs: set up, warm up, time
+--steps steps, print. --full adds the CPU baseline (cpu_baseline in the line,
+--cpu-seconds on the host's cores after the timed region). --dump-outputs DIR
+writes the output set of the last timed step and the timed region's counters
+as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -156,8 +163,19 @@ def parse(argv=None):
                          "--prefault-ms (page translations resident, GPU clocks up after the idle "
                          "process start); 0: off")
     ap.add_argument("--prefault-ms", type=float, default=250.0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline (cpu_baseline, "
+                         "--cpu-seconds of the host's cores after the timed region). Off by default: a plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in its output buffers "
+                         "(this rank's verdicts, hashes, partition, ...) and the counters of the timed region "
+                         "as DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed seeded sample of "
+                         "anything larger); ranks > 0 write DIR/<name>.rank<r>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: the CPU baseline's run time")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="kept for scripts written before --full: leaves the CPU baseline out, which a run "
+                         "without --full does anyway (with --full it cancels all that --full adds)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     a = ap.parse_args(argv)
     if a.workload is None:
@@ -591,6 +609,7 @@ class DeviceProcessor:
                 if time.perf_counter() >= t_end:
                     break
         warm = self._jobs(0, steps)
+        self.first = steps
         self.timed = self._jobs(steps, self.args.steps)   # built before the warmup
         # creates the event pool now, and times every warmup launch: the first
         # launch with timing events pays a one-time cost in HIP (~9 us of host
@@ -638,6 +657,17 @@ class DeviceProcessor:
         ms, cnt = self.ctx.read_timing()
         return dict(k_rx_ms=ms[0] / max(cnt[0], 1), k_scan_ms=ms[1] / max(cnt[1], 1),
                     k_part_ms=ms[2] / max(cnt[2], 1), launches=cnt)
+
+    def outputs(self):
+        """--dump-outputs: the output set of the last timed step, as the caller
+        of fcgpu_process_jobs finds it (after sync())."""
+        if self.args.steps < 1:
+            return {}
+        k = self.first + self.args.steps - 1
+        out = self.outs[k % len(self.outs)].numpy()
+        for derived in ("reason", "port"):      # both are fields of verdict
+            out.pop(derived, None)
+        return out
 
     def close(self):
         self.ctx.close()
@@ -716,6 +746,7 @@ class ReshardProcessor:
                                       tile_perm=True, partition=N.PART_TILE, flowid=True)
         self.ctr = torch.zeros(N.CTR_SHARDS, N.NCOUNTERS, dtype=torch.int64, device=dev)
         self.received = 0
+        self.last_m = 0
         self.stage_ms = [0.0] * 5
         self.ev = None
         self.timed_steps = 0
@@ -794,6 +825,7 @@ class ReshardProcessor:
         if ht is not None:
             h4 = time.perf_counter()
         f = self.flow_out
+        self.last_m = None       # the batch's size is on the device (fcount)
         bound = self.world * self.recs
         for c0 in range(0, bound, self.cap):
             self.ctx_flow.process_counted(rbuf.data_ptr(), self.fdesc[c0:].data_ptr(), min(self.cap, bound - c0),
@@ -853,6 +885,8 @@ class ReshardProcessor:
         f = self.flow_out
         if not process:          # a replayed step this rank's table already took
             m = 0
+        else:
+            self.last_m = m      # host-known size of the batch in flow_out (outputs())
         for c0 in range(0, m, self.cap):
             k = min(self.cap, m - c0)
             self.ctx_flow.process(buf.data_ptr(), rdesc[c0:].data_ptr(), k, stream=s.cuda_stream, **f.ptrs())
@@ -892,6 +926,17 @@ class ReshardProcessor:
 
     def timing(self):
         return None
+
+    def outputs(self):
+        """--dump-outputs: the flow pass's per-packet outputs over the last
+        chunk (at most FCGPU_FLOW_MAX_BATCH packets) of the batch this rank
+        received in the last timed step."""
+        m = self.last_m if self.last_m is not None else int(self.fcount.item())
+        if m <= 0:
+            return {}
+        valid = m - (m - 1) // self.cap * self.cap
+        out = self.flow_out.numpy()
+        return {k: out[k][:valid] for k in ("verdict", "hash", "flowid", "tile_perm")}
 
     def post_check(self, backend):
         """After the timed region: every rank's table holds exactly the flows
@@ -962,6 +1007,28 @@ def _diag_regions(proc, elapsed, enq, timing, repeats=6):
     proc.counters().copy_(snap)
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this much in all
+
+
+def write_outputs(path, arrays, rank=0):
+    """--dump-outputs: every array as path/<name>.npy (ranks > 0:
+    <name>.rank<r>.npy). Integers become float32 where it holds them exactly
+    (up to 16 bits), else float64. An array over its share of DUMP_BYTES is
+    cut to a sample of its elements at fixed, seeded, ascending positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.dtype.names:           # records: as their bytes
+            a = a.view(np.uint8)
+        a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        keep = share // a.dtype.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(64).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def rank_main(args, processor_factory, *, world, rank, gpu, backend, dev_for_collectives):
     """One rank of the benchmark: build, warm up, time exactly args.steps
     steps between barrier + device sync on both sides, take the max over
@@ -996,6 +1063,7 @@ def rank_main(args, processor_factory, *, world, rank, gpu, backend, dev_for_col
             _diag_regions(proc, elapsed, t_enq - t0, timing)
         maintain_ms = getattr(proc, "maintain_ms", None)
         post = proc.post_check(backend) if hasattr(proc, "post_check") else None
+        dump = proc.outputs() if getattr(args, "dump_outputs", None) and hasattr(proc, "outputs") else None
 
         # after the timed region: max time over ranks, counters summed over
         # ranks (RCCL all-reduce of the device vector), per-output offsets
@@ -1030,6 +1098,8 @@ def rank_main(args, processor_factory, *, world, rank, gpu, backend, dev_for_col
         raise AssertionError(f"valid count {valid} != {expect_valid}")
     if not np.array_equal(gtot, gv[N.CTR_PORT:N.CTR_PORT + nb].astype(np.int64)):
         raise AssertionError("all-gathered per-output counts disagree with the all-reduced counters")
+    if dump is not None:
+        write_outputs(args.dump_outputs, dict(dump, counters=gv), rank)
     if rank != 0:
         return None
     mpps = total_pkts / elapsed / 1e6
@@ -1075,7 +1145,7 @@ def rank_main(args, processor_factory, *, world, rank, gpu, backend, dev_for_col
                     scan_ms=round(timing["k_scan_ms"], 5), part_ms=round(timing["k_part_ms"], 5),
                     sampled_batches=timing["launches"][0])
     cpu = None
-    if world == 1 and not args.no_cpu and args.workload in ("c2", "c3", "c4") and not args.flow_capacity \
+    if args.full and world == 1 and not args.no_cpu and args.workload in ("c2", "c3", "c4") and not args.flow_capacity \
             and not args.flow_reshard and args.classify in ("lb", "ipclass16"):   # the chains the port runs
         cpu = cpu_baseline(args.cpu_seconds, flows=dict(c2=1, c3=10000).get(args.workload, 4096),
                            program=ipclass16_program() if args.classify == "ipclass16" else None)

@@ -1,5 +1,8 @@
 """The FastClick package element (fastclick_pkg/) compiled against the
-reference's own headers.
+reference's own headers. Not part of the test suite: it needs a FastClick
+source tree, which this repository does not hold. Run it by hand with
+
+    FASTCLICK_SRC=/path/to/fastclick python -m pytest fastclick_pkg/check_reference.py
 
 The reference's configure is not run; fastclick_pkg/gen_config.py makes the
 two headers it would generate (click/config.h, click/config-userlevel.h) by
@@ -7,11 +10,10 @@ config.status's `#undef` substitution over the reference's config.h.in and
 config-userlevel.h.in, for a userlevel x86-64 build with batching, flows and
 IPv6. The element, its ClickPolicy over FastClick's Packet / PacketBatch /
 Timer / per_thread, and the shared RxCore then compile to an object with
-g++ against /root/reference/include (-Wall -Wextra -Werror) -- every FastClick
+g++ against FASTCLICK_SRC/include (-Wall -Wextra -Werror) -- every FastClick
 declaration the package uses, with the argument types it passes. A mutated
 copy with one API misuse must fail, so the check is not vacuous.
 
-CPU only; skipped where the reference tree is absent (the GPU box).
 Reference interface: include/click/batchelement.hh:29-125,
 include/click/packetbatch.hh:631, include/click/sync.hh:56-203,
 include/click/timer.hh:158.
@@ -23,12 +25,12 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-PKG = os.path.join(ROOT, "fastclick_pkg")
+PKG = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(PKG)
+REF = os.environ.get("FASTCLICK_SRC", "")
 
 pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "config.h.in")),
-                                reason="reference tree not present")
+                                reason="set FASTCLICK_SRC to a FastClick source tree")
 
 
 def _config(tmp):

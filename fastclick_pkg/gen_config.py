@@ -14,7 +14,7 @@ stays undefined, as configure leaves an absent feature.
     python3 fastclick_pkg/gen_config.py REFERENCE_DIR OUT_DIR
         -> OUT_DIR/click/config.h, OUT_DIR/click/config-userlevel.h
 
-Only tests use it (tests/test_fastclick_pkg.py): it produces headers for
+Only fastclick_pkg/check_reference.py uses it: it produces headers for
 `g++ -fsyntax-only`, never a FastClick build.
 """
 from __future__ import annotations

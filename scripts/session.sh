@@ -43,7 +43,7 @@ for s in "${ST[@]}"; do
     tests_sel) step pytest_sel 600 python -u -m pytest $SEL -m gpu -x -v --timeout 120 --timeout-method thread ;;
     tests_flow) step pytest_flow 600 python -u -m pytest tests/test_flow.py tests/test_flow_imp.py -m gpu -x -v --timeout 120 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 300 python bench.py $DRV ;;
+    bench) step bench 300 python bench.py $DRV --full ;;
     bench_s1) step bench_s1 300 python bench.py $DRV --streams 1 --fuse 1 --no-cpu ;;
     bench_long) step bench_long 300 python bench.py --steps 200 --warmup 20 --no-cpu ;;
     bench_long_s1) step bench_long_s1 300 python bench.py --steps 200 --warmup 20 --no-cpu --streams 1 --fuse 1 ;;

@@ -355,7 +355,8 @@ def test_gpu_alloc_fault_pool_register(oracle, alloc_fault, skip):
     refuses, no launch), the next registration works and the mbuf batch
     equals the oracle."""
     from fastclick_amd.device import DeviceOutputs
-    from tests.test_mbuf import make_pool
+    from tests.test_mbuf import make_pool, require_host_register
+    require_host_register()
     b = _batch(3000, seed=61)
     buf, arr, base, size, ptrs = make_pool(b.frames(), np.random.default_rng(62))
     cfg = _cfg()
