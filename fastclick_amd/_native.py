@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 25
+ABI_VERSION = 26
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -34,7 +34,7 @@ def reason_slot(r: int) -> int:
     return r if r < 6 else r - 1
 CHECK_IP4, MARK_IP4, CHECK_AUTO, MARK_IP6 = 0, 1, 2, 3
 HASH_NONE, HASH_FLOWID, HASH_FLOW5ID = 0, 1, 2
-CLS_NONE, CLS_LB_HASH, CLS_HASH_IP, CLS_HASHSWITCH, CLS_PROGRAM, CLS_LB_CRC, CLS_LB_TABLE = 0, 1, 2, 3, 4, 5, 6
+CLS_NONE, CLS_LB_HASH, CLS_HASH_IP, CLS_HASHSWITCH, CLS_PROGRAM, CLS_LB_CRC, CLS_LB_TABLE, CLS_ROUTE = range(8)
 PROG_IPFILTER, PROG_CLASSIFIER = 0, 1
 STEP_SHORT_YES = 1
 MAX_STEPS = 8192
@@ -204,6 +204,8 @@ FCGPU_SYMBOLS = {
                                     C.c_int32]),
     "fcgpu_set_lb_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "fcgpu_lb_hash_ring": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
+    "fcgpu_set_routes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_route_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fcgpu_set_host_threads": (C.c_int, [C.c_void_p, C.c_uint32]),
     "fcgpu_span_submit": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                     C.POINTER(fcgpu_out)]),
@@ -303,6 +305,45 @@ def lb_hash_ring(nsel: int, size: int | None = None):
     if rc != OK:
         raise ValueError(f"fcgpu_lb_hash_ring({nsel}, {size}) failed ({rc})")
     return out
+
+
+def route_dtype():
+    """numpy dtype of fcgpu_route."""
+    import numpy as np
+    return np.dtype([("addr", "<u4"), ("gw", "<u4"), ("plen", "u1"), ("port", "u1"), ("reserved", "<u2")])
+
+
+def routes_array(routes):
+    """fcgpu_route records (a numpy structured array) from a sequence of
+    (addr, plen, gw, port): addr and gw dotted quads or raw network-order
+    words (raw_addr), gw 0 / None = no gateway. An array of that dtype passes
+    through."""
+    import numpy as np
+    dt = route_dtype()
+    if isinstance(routes, np.ndarray) and routes.dtype == dt:
+        return np.ascontiguousarray(routes)
+    out = np.zeros(len(routes), dt)
+    for k, (addr, plen, gw, port) in enumerate(routes):
+        if not (0 <= int(plen) <= 255 and 0 <= int(port) <= 255):
+            raise ValueError(f"route {k}: prefix length or output out of range")
+        out[k] = (raw_addr(addr) if isinstance(addr, str) else addr,
+                  raw_addr(gw) if isinstance(gw, str) else (gw or 0), plen, port, 0)
+    return out
+
+
+def route_lookup(routes, addr, nports: int = 0):
+    """fcgpu_route_lookup: (port, gw) of addr's longest matching prefix in
+    `routes` (routes_array's forms), port -1 and gw 0 without a route; gw is a
+    raw network-order word. The trie is built and walked as on the device.
+    Host-only. Raises ValueError for a route list fcgpu_set_routes refuses."""
+    r = routes_array(routes)
+    gw = C.c_uint32(0)
+    lib = load()
+    port = lib.fcgpu_route_lookup(r.ctypes.data, len(r), nports, raw_addr(addr) if isinstance(addr, str) else addr,
+                                  C.byref(gw))
+    if port < -1:
+        raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
+    return port, gw.value
 
 
 def default_cfg() -> fcgpu_cfg:
@@ -482,6 +523,12 @@ class Context:
             arr[i] = st if isinstance(st, fcgpu_step) else fcgpu_step(*[int(x) for x in st])
         self._chk(self.lib.fcgpu_set_program(self.h, kind, arr, len(steps), output_everything),
                   "fcgpu_set_program")
+
+    def set_routes(self, routes):
+        """The route table of CLS_ROUTE (routes_array's forms); replaces the
+        previous one."""
+        r = routes_array(routes)
+        self._chk(self.lib.fcgpu_set_routes(self.h, r.ctypes.data, len(r)), "fcgpu_set_routes")
 
     def set_lb_table(self, table):
         """The bucket -> output table of CLS_LB_TABLE (uint8 sequence)."""

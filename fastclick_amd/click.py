@@ -25,7 +25,7 @@ class fcclick_event(C.Structure):
 
 EV_BURST, EV_READ = 0, 1
 HANDLERS = ("count", "drops", "drop_details", "port_counts", "flow_count", "flow_count_fids", "flow_drops",
-            "gpu_errors", "gpu_retries", "error")
+            "gpu_errors", "gpu_retries", "error", "table")
 
 
 class fcclick_result(C.Structure):

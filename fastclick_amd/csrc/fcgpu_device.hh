@@ -57,6 +57,9 @@ struct DevCfg {
     const uint8_t *lb_tab;    // FCGPU_CLS_LB_TABLE: bucket -> output ((lb_tab_n + 15) & ~15 bytes, zero-padded)
     uint32_t lb_tab_n;        // buckets (<= 65536: the folded hash is < 2^16)
     uint32_t lb_tab_magic;    // ceil(2^32 / lb_tab_n) for lb_port's fastmod
+    const uint16_t *rt;       // FCGPU_CLS_ROUTE: l0[65536], then the chunk pool (host/route_table.hh)
+    uint32_t rt_hop_off;      // byte offset of the next hops ({gw, port}, 8 B each) from rt
+    uint32_t rt_nhops;        // next hops, entry 0 (no route) included
 };
 
 // Device step: x = (u16)offset | flags << 16, y = value, z = mask,
@@ -255,6 +258,49 @@ __device__ __forceinline__ uint32_t lb_table_port(const DevCfg &c, const uint4 *
     return p;
 }
 
+// ---- FCGPU_CLS_ROUTE: IPRouteTable::lookup_route over the 16-8-8 trie -------
+// (host/route_table.hh has the structure and its builder)
+// The first load depends only on the packet's ip_dst word, so the callers
+// issue it as soon as that word is in registers -- before the checksum fold
+// and the reason chain, and for packets that turn out invalid too: the index
+// is the address's top 16 bits, in range for any word -- and walk the rest
+// when they classify. A prefix of /16 or shorter ends at that load.
+constexpr uint32_t kRtChunks = 65536;       // uint16 index of the chunk pool in DevCfg::rt
+constexpr uint32_t kRtNoPort = 0xffffffffu; // next hop 0's port
+__device__ __forceinline__ uint32_t route_probe(const DevCfg &c, uint32_t dst_raw) {
+    return c.rt[__builtin_bswap32(dst_raw) >> 16];
+}
+// e0: route_probe's entry. Returns the next hop {gw, port}: from the
+// workgroup's LDS copy (dyn != nullptr: at most 512 next hops) or from global
+// memory -- two branches, not a pointer select, and the vector-memory count
+// drained before the join, for lb_table_port's reason above.
+__device__ __forceinline__ uint2 route_walk(const DevCfg &c, const uint4 *dyn, uint32_t dst_raw, uint32_t e0) {
+    const uint32_t a = __builtin_bswap32(dst_raw);
+    uint32_t e = e0;
+    if (e & 0x8000u) {
+        e = c.rt[kRtChunks + ((e & 0x7fffu) << 8) + ((a >> 8) & 0xffu)];
+        if (e & 0x8000u) e = c.rt[kRtChunks + ((e & 0x7fffu) << 8) + (a & 0xffu)];
+    }
+    if (dyn) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): e is needed here anyway
+        return reinterpret_cast<const uint2 *>(dyn)[e];
+    }
+    const uint2 h = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(c.rt) + c.rt_hop_off)[e];
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    return h;
+}
+// IPRouteTable::process (iproutetable.cc:152-169) on a packet that passed the
+// checks: the output, the gateway into the DST_IP annotation; no route kills
+// the packet as an unmatched program does (CLASSIFY_EACH_PACKET, port nports).
+__device__ __forceinline__ uint32_t route_apply(const DevCfg &c, uint2 hop, fcgpu_anno &an, uint32_t &reason) {
+    if (hop.y >= c.nports) {                 // kRtNoPort (or an output the submission check refuses)
+        reason = FCGPU_R_NO_MATCH;
+        return c.nports;
+    }
+    if (hop.x) an.dst_ip = hop.x;
+    return hop.y;
+}
+
 // rte_hash_crc_4byte(data, crc) (DPDK rte_hash_crc.h: _mm_crc32_u32(crc, data)):
 // CRC32-C, reflected polynomial 0x82F63B78, no inversion -- a reflected CRC
 // takes the 32-bit word at once (xor) and shifts it through bit by bit.
@@ -408,9 +454,13 @@ __host__ __device__ inline bool crc_in_lds(const DevCfg &c) { return c.classify 
 __host__ __device__ inline bool tab_in_lds(const DevCfg &c) {
     return c.classify == FCGPU_CLS_LB_TABLE && c.lb_tab && c.lb_tab_n <= kTabLdsBytes;
 }
+// FCGPU_CLS_ROUTE: the next hops (8 B each) when they fit the same 4 KB
+__host__ __device__ inline bool hops_in_lds(const DevCfg &c) {
+    return c.classify == FCGPU_CLS_ROUTE && c.rt && c.rt_nhops * 8u <= kTabLdsBytes;
+}
 inline size_t prog_lds_bytes(const DevCfg &c) {
     return prog_in_lds(c) ? sizeof(uint4) * c.prog_q : crc_in_lds(c) ? sizeof(uint4) * kCrcTabQ
-         : tab_in_lds(c) ? (c.lb_tab_n + 15u) & ~15u : 0;
+         : tab_in_lds(c) ? (c.lb_tab_n + 15u) & ~15u : hops_in_lds(c) ? (c.rt_nhops * 8u + 15u) & ~15u : 0;
 }
 #ifdef FCGPU_JIT_PROGRAM
 // The installed program compiled to straight-line code (fcgpu_program_jit,
@@ -506,7 +556,7 @@ __device__ __forceinline__ uint32_t check_ip6(const DevCfg &c, const FrameView &
     return FCGPU_R_OK;
 }
 
-template <int CM, bool CK, bool PROG>
+template <int CM, bool CK, bool PROG, bool ROUTE = false>
 __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView &f, uint32_t len,
                                                PktResult &r, const uint4 *sprog) {
     fcgpu_anno &an = r.an;
@@ -571,6 +621,11 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
         }
     }
     r.hash = hv;
+    if (ROUTE) {   // FCGPU_CLS_ROUTE (IPv4 check modes): the general path probes once the checks are done
+        an.dst_ip = h[4];   // the chain's GetIPAddress(16): MarkIPHeader alone leaves the annotation unset
+        r.port = route_apply(c, route_walk(c, sprog, h[4], route_probe(c, h[4])), an, r.reason);
+        return;
+    }
     switch (c.classify) {
     case FCGPU_CLS_LB_HASH: r.port = (uint32_t)lb_port(hv, c.nports, c.lb_magic); break;
     case FCGPU_CLS_LB_CRC: {
@@ -607,7 +662,7 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
 // branches except the (wave-uniform) configuration. Returns false when this
 // lane needs the general path (options, header beyond the window, hash modes
 // or classifiers it does not cover); the caller then runs process_packet.
-template <bool CK, bool PROG>
+template <bool CK, bool PROG, bool ROUTE = false>
 __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, uint32_t len, uint32_t o, PktResult &r,
                                          const uint4 *sprog) {
     const uint32_t x = f.shift + o, a = x & ~3u, sh = x & 3u;
@@ -620,6 +675,9 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
     uint32_t h[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) h[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
+    // FCGPU_CLS_ROUTE: the trie's first entry, loaded while the checks run
+    uint32_t rt0 = 0;
+    if (ROUTE) rt0 = route_probe(c, h[4]);
     // CheckIPHeader::valid reason chain, computed as predicates (no divergent
     // branches); the first failing check wins, as in the reference
     const uint32_t plen = len - o;
@@ -657,7 +715,9 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
         if (c.hash_mode == FCGPU_HASH_FLOW5ID) hv ^= (h[2] >> 8) & 0xff;
     }
     uint32_t port = 0;
-    if (c.classify == FCGPU_CLS_LB_HASH) {
+    if (ROUTE) {
+        // below, with the annotation the gateway goes into
+    } else if (c.classify == FCGPU_CLS_LB_HASH) {
         port = (uint32_t)lb_port(hv, c.nports, c.lb_magic);
     } else if (c.classify == FCGPU_CLS_LB_CRC) {       // wave-uniform
         const bool first = (bswap16(h[1] >> 16) & 0x1fff) == 0;
@@ -689,6 +749,7 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
         port = run_program(c, f, an, sprog);
         if (port >= c.nports) r.reason = FCGPU_R_NO_MATCH;
     }
+    if (ROUTE && ok) port = route_apply(c, route_walk(c, sprog, h[4], rt0), an, r.reason);
     r.port = ok && port < c.nports ? port : c.nports;
     return true;
 }
@@ -1332,7 +1393,7 @@ __device__ __forceinline__ RxView rx_view(const RxArgs &A) {
 // classify; per-wave histogram by ballots; counters by sharded atomics;
 // optionally the tile's stable per-output partition (CLASSIFY_EACH_PACKET on a
 // 256-packet PacketBatch).
-template <int CM, bool CK, int PART, bool PROG, bool L4, bool FAST, bool FLOW>
+template <int CM, bool CK, int PART, bool PROG, bool L4, bool FAST, bool FLOW, bool ROUTE = false>
 __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const FlowArgs &FL, uint32_t tile, uint2 d,
                                         const uint8_t *wl,
                                         uint32_t (*s_cnt)[kMaxBins], const uint4 *sprog) {
@@ -1350,11 +1411,11 @@ __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const 
     uint32_t bin = 0xffffffffu, rslot = 0xffffffffu;
     if (FAST && CM == FCGPU_CHECK_IP4) {
         bool done = !live;
-        if (live) done = ip4_fast<CK, PROG>(A.cfg, f, d.y, (uint32_t)A.cfg.offset, r, sprog);
+        if (live) done = ip4_fast<CK, PROG, ROUTE>(A.cfg, f, d.y, (uint32_t)A.cfg.offset, r, sprog);
         if (__ballot(!done)) {
             if (!done) {
                 r.an = fcgpu_anno{};
-                process_packet<CM, CK, PROG>(A.cfg, f, d.y, r, sprog);
+                process_packet<CM, CK, PROG, ROUTE>(A.cfg, f, d.y, r, sprog);
             }
         }
     } else if (FAST && CM == FCGPU_CHECK_AUTO) {
@@ -1367,7 +1428,7 @@ __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const 
             }
         }
     } else if (live) {
-        process_packet<CM, CK, PROG>(A.cfg, f, d.y, r, sprog);
+        process_packet<CM, CK, PROG, ROUTE>(A.cfg, f, d.y, r, sprog);
     }
     if (L4) l4_stage(A.cfg, f, V.arena + d.x, live, r);
     FlowProbe fq;
@@ -1491,12 +1552,15 @@ struct RxLaunch {
     RxJob job[kMaxFuse];
 };
 
+// ROUTE: the FCGPU_CLS_ROUTE classifier, compiled only into the kernels
+// launched for it (IPv4 check modes), as PROG is for decision programs: the
+// other instances keep their classify chain as it was.
 template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false,
-          bool FAST = (CM == FCGPU_CHECK_IP4 || CM == FCGPU_CHECK_AUTO)>
+          bool FAST = (CM == FCGPU_CHECK_IP4 || CM == FCGPU_CHECK_AUTO), bool ROUTE = false>
 __global__ __launch_bounds__(kTile, 8) void k_rx(RxLaunch L) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[4 * kWave * kWin];
     __shared__ uint32_t s_cnt[4][kMaxBins];
-    extern __shared__ uint4 s_prog[];           // prog_lds_bytes(cfg) at launch: program steps, CRC or LB tables
+    extern __shared__ uint4 s_prog[];           // prog_lds_bytes(cfg) at launch: program steps, CRC or LB tables, next hops
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RxArgs &A = L.A;
     RxView V = rx_view(A);
@@ -1556,12 +1620,17 @@ __global__ __launch_bounds__(kTile, 8) void k_rx(RxLaunch L) {
     if (crc_lds && threadIdx.x < kCrcTabQ) s_prog[threadIdx.x] = A.cfg.crc_tab[threadIdx.x];
     if (tab_lds && threadIdx.x * 16u < A.cfg.lb_tab_n)
         s_prog[threadIdx.x] = reinterpret_cast<const uint4 *>(A.cfg.lb_tab)[threadIdx.x];
+    // next hops of a route table: two per thread, the device image is padded to 16 B
+    const bool hop_lds = ROUTE && hops_in_lds(A.cfg);         // block-uniform
+    if (hop_lds && threadIdx.x * 2u < A.cfg.rt_nhops)
+        s_prog[threadIdx.x] = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(A.cfg.rt) +
+                                                              A.cfg.rt_hop_off)[threadIdx.x];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (every wave copying the whole table by LDS-DMA instead, with no block
     // barrier, measured the same: profiles/r05_lb/nobarrier_*)
-    const bool dyn = prog_lds || crc_lds || tab_lds;
+    const bool dyn = prog_lds || crc_lds || tab_lds || hop_lds;
     if (dyn) __syncthreads();
-    rx_tile<CM, CK, PART, PROG, L4, FAST, FLOW>(A, V, FL, tile, d, wl, s_cnt, dyn ? s_prog : nullptr);
+    rx_tile<CM, CK, PART, PROG, L4, FAST, FLOW, ROUTE>(A, V, FL, tile, d, wl, s_cnt, dyn ? s_prog : nullptr);
 }
 
 

@@ -220,6 +220,10 @@ struct fcgpu_ctx {
     uint8_t *d_lbtab = nullptr;               // LB_TABLE bucket -> output (fcgpu_set_lb_table)
     uint32_t lbtab_n = 0, lbtab_max = 0;      // its buckets and largest output
     uint64_t lbtab_key = 0;                   // hash of its contents (0: none)
+    uint8_t *d_routes = nullptr;              // CLS_ROUTE trie image (fcgpu_set_routes, host/route_table.hh)
+    uint32_t rt_hop_off = 0, rt_nhops = 0;    // its next hops: byte offset, count (0: no table)
+    uint32_t rt_max_port = 0;                 // largest output of any route
+    uint64_t rt_key = 0;                      // hash of the image (0: none)
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)

@@ -18,7 +18,7 @@ static_assert(kCrcTabQ <= kTile, "k_rx copies the CRC tables with one uint4 per 
 // L: one batch (njobs 1, grid = its tiles) or several fused ones (grid =
 // their tiles end to end).
 
-template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false>
+template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false, bool ROUTE = false>
 static void launch_rx(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
                       fcgpu_ctx *jc) {
     if (PROG && jc) {   // the program compiled to code, when the context has it
@@ -31,26 +31,41 @@ static void launch_rx(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_
             return;
         }
     }
-    const size_t lds = prog_lds_bytes(L.A.cfg);   // program steps (PROG), CRC tables (LB_CRC), LB table, else 0
+    // program steps (PROG), CRC tables (LB_CRC), LB table, next hops (ROUTE), else 0
+    const size_t lds = prog_lds_bytes(L.A.cfg);
+    constexpr bool FAST = CM == FCGPU_CHECK_IP4 || CM == FCGPU_CHECK_AUTO;
     if (ev0)
-        hipExtLaunchKernelGGL((k_rx<CM, CK, PART, PROG, L4, FLOW>), dim3(grid), dim3(kTile), lds, s, ev0, ev1,
-                              0, L);
+        hipExtLaunchKernelGGL((k_rx<CM, CK, PART, PROG, L4, FLOW, FAST, ROUTE>), dim3(grid), dim3(kTile), lds, s, ev0,
+                              ev1, 0, L);
     else
-        hipLaunchKernelGGL((k_rx<CM, CK, PART, PROG, L4, FLOW>), dim3(grid), dim3(kTile), lds, s, L);
+        hipLaunchKernelGGL((k_rx<CM, CK, PART, PROG, L4, FLOW, FAST, ROUTE>), dim3(grid), dim3(kTile), lds, s, L);
 }
 
 // IPv4 check modes: L4 (CheckUDPHeader/CheckTCPHeader) and the flow table
 // exist only there (fcgpu_configure / fcgpu_process reject them with CHECK_AUTO).
-template <int CM, bool CK, int PART, bool PROG>
+template <int CM, bool CK, int PART, bool PROG, bool ROUTE = false>
 static void launch_rx_ip4(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1, fcgpu_ctx *jc) {
     const bool l4 = L.A.cfg.l4_mode != FCGPU_L4_NONE, flow = L.A.fl.slots != nullptr;
     if (flow) {
-        if (l4) launch_rx<CM, CK, PART, PROG, true, true>(L, grid, s, e0, e1, jc);
-        else launch_rx<CM, CK, PART, PROG, false, true>(L, grid, s, e0, e1, jc);
+        if (l4) launch_rx<CM, CK, PART, PROG, true, true, ROUTE>(L, grid, s, e0, e1, jc);
+        else launch_rx<CM, CK, PART, PROG, false, true, ROUTE>(L, grid, s, e0, e1, jc);
     } else {
-        if (l4) launch_rx<CM, CK, PART, PROG, true>(L, grid, s, e0, e1, jc);
-        else launch_rx<CM, CK, PART, PROG, false>(L, grid, s, e0, e1, jc);
+        if (l4) launch_rx<CM, CK, PART, PROG, true, false, ROUTE>(L, grid, s, e0, e1, jc);
+        else launch_rx<CM, CK, PART, PROG, false, false, ROUTE>(L, grid, s, e0, e1, jc);
     }
+}
+
+// FCGPU_CLS_ROUTE: its own instances of the IPv4 check modes (the route walk is
+// compiled into no other kernel); fcgpu_configure refuses the mode elsewhere.
+template <int PART>
+static hipError_t launch_rx_route(uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0,
+                                  hipEvent_t e1) {
+    if (!L.A.cfg.rt || !L.A.cfg.rt_nhops) return hipErrorInvalidValue;
+    if (cm == FCGPU_MARK_IP4) launch_rx_ip4<FCGPU_MARK_IP4, false, PART, false, true>(L, grid, s, e0, e1, nullptr);
+    else if (cm != FCGPU_CHECK_IP4) return hipErrorInvalidValue;
+    else if (ck) launch_rx_ip4<FCGPU_CHECK_IP4, true, PART, false, true>(L, grid, s, e0, e1, nullptr);
+    else launch_rx_ip4<FCGPU_CHECK_IP4, false, PART, false, true>(L, grid, s, e0, e1, nullptr);
+    return hipSuccess;
 }
 
 template <int PART, bool PROG>
@@ -105,6 +120,10 @@ bool rx_launch_ok(int part, const RxLaunch &L, uint32_t grid) {
 hipError_t launch_rx_any(int part, uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0,
                           hipEvent_t e1, fcgpu_ctx *jc) {
     if (!rx_launch_ok(part, L, grid)) return hipErrorInvalidValue;
+    if (L.A.cfg.classify == FCGPU_CLS_ROUTE)
+        return part == kPartTile     ? launch_rx_route<kPartTile>(cm, ck, L, grid, s, e0, e1)
+               : part == kPartGlobal ? launch_rx_route<kPartGlobal>(cm, ck, L, grid, s, e0, e1)
+                                     : launch_rx_route<kPartNone>(cm, ck, L, grid, s, e0, e1);
     if (L.A.cfg.classify == FCGPU_CLS_PROGRAM) launch_rx_prog<true>(part, cm, ck, L, grid, s, e0, e1, jc);
     else launch_rx_prog<false>(part, cm, ck, L, grid, s, e0, e1, jc);
     return hipSuccess;

@@ -1,8 +1,10 @@
 // fcgpu_program.hip -- decision programs (FCGPU_CLS_PROGRAM: IPFilter /
 // IPClassifier / Classifier): upload with jump tables
 // (build_tables), compiled programs (fcgpu_program_jit, hiprtc through
-// prog_jit.hh), and the LoadBalancer hash tables (FCGPU_CLS_LB_TABLE).
+// prog_jit.hh), the LoadBalancer hash tables (FCGPU_CLS_LB_TABLE) and the
+// route table (FCGPU_CLS_ROUTE).
 #include "fcgpu_internal.hh"
+#include "host/route_table.hh"
 #include "jit_sources.inc"   // kJitDeviceHh, kJitAbiH (fastclick_amd/build.py)
 
 using namespace fcgpu;
@@ -273,6 +275,52 @@ int fcgpu_set_lb_table(fcgpu_ctx *c, const uint8_t *table, uint32_t nbuckets) {
     d.lb_tab_n = n;
     d.lb_tab_magic = n > 1 ? (uint32_t)((((uint64_t)1 << 32) + n - 1) / n) : 0u;
     return FCGPU_OK;
+}
+
+// FCGPU_CLS_ROUTE: the trie is built on the host (host/route_table.hh) and
+// uploaded as one image; same contract as fcgpu_set_lb_table.
+int fcgpu_set_routes(fcgpu_ctx *c, const fcgpu_route *routes, uint32_t n) {
+    if (!c) return FCGPU_EINVAL;
+    if (!routes && n) return fail(c, FCGPU_EINVAL, "fcgpu_set_routes: null routes");
+    if (agg_queued(c)) return fail(c, FCGPU_EINVAL, "fcgpu_set_routes: a queued span submission is not waited for");
+    fcroute::Table t;
+    std::string why;
+    if (fcroute::build(routes, n, c->configured ? c->cfg.nports : 0, t, why) != FCGPU_OK)
+        return fail(c, FCGPU_EINVAL, "fcgpu_set_routes: " + why);
+    uint32_t hop_off = 0;
+    const std::vector<uint8_t> img = fcroute::image(t, hop_off);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    // uploaded before the old table is freed: a failure leaves it intact
+    uint8_t *nt = nullptr;
+    if (int rc = alloc_or_fail(c, "fcgpu_set_routes", {dev_buf(nt, img.size())})) return rc;
+    if (hipError_t e = hipMemcpy(nt, img.data(), img.size(), hipMemcpyHostToDevice)) {
+        (void)hipFree(nt);
+        return fail(c, FCGPU_ERUNTIME, std::string("fcgpu_set_routes upload: ") + hipGetErrorString(e));
+    }
+    hipFree(c->d_routes);
+    c->d_routes = nt;
+    c->rt_hop_off = hop_off;
+    c->rt_nhops = (uint32_t)t.hops.size();
+    c->rt_max_port = t.max_port;
+    uint64_t key = 1469598103934665603ull;
+    for (uint8_t b : img) key = (key ^ b) * 1099511628211ull;
+    c->rt_key = (key ^ img.size()) | 1;
+    DevCfg &d = c->dcfg;
+    d.rt = c->cfg.classify == FCGPU_CLS_ROUTE ? reinterpret_cast<const uint16_t *>(c->d_routes) : nullptr;
+    d.rt_hop_off = hop_off;
+    d.rt_nhops = c->rt_nhops;
+    return FCGPU_OK;
+}
+
+int fcgpu_route_lookup(const fcgpu_route *routes, uint32_t n, uint32_t nports, uint32_t addr, uint32_t *gw) {
+    fcroute::Table t;
+    std::string why;
+    if ((!routes && n) || fcroute::build(routes, n, nports, t, why) != FCGPU_OK) {
+        fail(nullptr, FCGPU_EINVAL, "fcgpu_route_lookup: " + (why.empty() ? std::string("null routes") : why));
+        return -2;
+    }
+    return fcroute::lookup(t, addr, gw);
 }
 
 int fcgpu_program_jit(fcgpu_ctx *c, int enable) {

@@ -26,10 +26,12 @@ inline std::vector<std::string> split_conf(const std::string &s) {
     std::vector<std::string> out;
     std::string cur;
     int depth = 0;
+    bool quoted = false;      // commas inside "..." do not split (cp_argvec)
     for (char c : s) {
-        if (c == '(') depth++;
-        if (c == ')') depth--;
-        if (c == ',' && depth == 0) {
+        if (c == '"') quoted = !quoted;
+        if (c == '(' && !quoted) depth++;
+        if (c == ')' && !quoted) depth--;
+        if (c == ',' && depth == 0 && !quoted) {
             out.push_back(trim(cur));
             cur.clear();
         } else {

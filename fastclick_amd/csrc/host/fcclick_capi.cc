@@ -176,7 +176,7 @@ static int run_graph(const char *conf, const uint8_t *arena, const uint32_t *des
 
 static const char *const kHandlerNames[] = {"count",      "drops",           "drop_details", "port_counts",
                                             "flow_count", "flow_count_fids", "flow_drops",   "gpu_errors",
-                                            "gpu_retries", "error"};
+                                            "gpu_retries", "error",           "table"};
 static std::string read_all(Element *el) {
     std::string h;
     for (const char *name : kHandlerNames) h += std::string(name) + "=" + el->read_handler(name) + "\n";

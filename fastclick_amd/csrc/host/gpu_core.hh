@@ -54,6 +54,12 @@
 //     (lines separated by newlines or '|', program_text.hh); N is the
 //     classifier's output count. Packets no rule matches are killed, as
 //     CLASSIFY_EACH_PACKET kills a packet whose port is out of range.
+//   ROUTES "ADDR/MASK [GW] OUT, ..."           -- StaticIPLookup behind GetIPAddress(16)
+//     (IPRouteTable::process, iproutetable.cc:152-169): each packet leaves on its
+//     longest matching prefix's OUT with GW, if any, in the DST_IP annotation; a
+//     packet with no route is killed. N defaults to the largest OUT + 1. Static:
+//     the `table` handler prints the routes, there are no write handlers. MODE
+//     CHECK or MARK; not with LB_MODE, HASHSWITCH or PROGRAM.
 //   L4 UDP|TCP, L4_CHECKSUM (default true)   -- CheckUDPHeader / CheckTCPHeader
 //     behind the IPv4 check (MODE CHECK or MARK); their drops join output N
 //   COLOR (PAINT annotation on every packet)  -- IPInputCombo (with OFFSET 14,
@@ -147,6 +153,9 @@ class RxCore {
         _cfg.checksum = 0;
         bool strip_set = false;
         bool have_if = false, badsrc_set = false, gooddst_set = false;
+        bool n_set = false, other_cls = false;     // N given; LB_MODE / HASHSWITCH / PROGRAM given
+        _routes.clear();
+        _routes_set = false;
         std::vector<uint32_t> if_bad, if_good;   // INTERFACES (raw network-order words)
         for (const auto &raw : conf) {
             ConfArg a = parse_arg(raw);
@@ -204,9 +213,15 @@ class RxCore {
             } else if (k == "N" || k == "NPORTS") {
                 if (!parse_int(v, n) || n < 1 || n > FCGPU_MAX_PORTS) return err(errh, "N out of range");
                 _cfg.nports = (uint32_t)n;
+                n_set = true;
                 if (_cfg.classify == FCGPU_CLS_NONE) _cfg.classify = FCGPU_CLS_LB_HASH;
+            } else if (k == "ROUTES") {
+                std::string e = parse_routes(v);
+                if (!e.empty()) return err(errh, "ROUTES: " + e);
+                _routes_set = true;
             } else if (k == "LB_MODE") {
                 // LoadBalancer modetrans (include/click/loadbalancer.hh:23-58)
+                other_cls = true;
                 _lb_direct = v == "hash";
                 if (v == "hash" || v == "hash_agg") _cfg.classify = FCGPU_CLS_LB_HASH;
                 else if (v == "hash_ip") _cfg.classify = FCGPU_CLS_HASH_IP;
@@ -230,6 +245,7 @@ class RxCore {
                 ss >> a1 >> a2;
                 if (!parse_int(a1, o) || !parse_int(a2, l) || l <= 0 || o < 0)
                     return err(errh, "HASHSWITCH expects OFFSET LENGTH (length must be > 0)");
+                other_cls = true;
                 _cfg.classify = FCGPU_CLS_HASHSWITCH;
                 _cfg.hs_offset = (int32_t)o;
                 _cfg.hs_length = (int32_t)l;
@@ -249,6 +265,7 @@ class RxCore {
                 if (text.size() >= 2 && text.front() == '"' && text.back() == '"') text = text.substr(1, text.size() - 2);
                 std::string e = parse_program(text, _prog);
                 if (!e.empty()) return err(errh, "PROGRAM: " + e);
+                other_cls = true;
                 _cfg.classify = FCGPU_CLS_PROGRAM;
             } else if (k == "PROGRAM_JIT") {
                 if (!parse_bool(v, _prog_jit)) return err(errh, "PROGRAM_JIT expects true/false");
@@ -364,6 +381,19 @@ class RxCore {
             for (size_t j = 0; j < if_good.size(); ++j) _cfg.gooddst[j] = if_good[j];
         }
         if (!strip_set) _strip = (_cfg.check_mode == FCGPU_CHECK_AUTO);
+        if (_routes_set) {
+            // IPRouteTable::configure (iproutetable.cc:102-124): outputs below
+            // noutputs; the table itself is checked as fcgpu_set_routes will
+            if (other_cls) return err(errh, "ROUTES conflicts with LB_MODE, HASHSWITCH and PROGRAM");
+            if (_cfg.check_mode != FCGPU_CHECK_IP4 && _cfg.check_mode != FCGPU_MARK_IP4)
+                return err(errh, "ROUTES needs MODE CHECK or MARK");
+            uint32_t top = 0;
+            for (const fcgpu_route &r : _routes) top = r.port > top ? r.port : top;
+            if (!n_set) _cfg.nports = top + 1;
+            _cfg.classify = FCGPU_CLS_ROUTE;
+            if (fcgpu_route_lookup(_routes.data(), (uint32_t)_routes.size(), _cfg.nports, 0, nullptr) < -1)
+                return err(errh, std::string("ROUTES: ") + fcgpu_last_error(nullptr));
+        }
         // The byte-sum classifiers read from p->data() (hashswitch.cc:52-59,
         // loadbalancer.hh:138-152,227-243): with STRIP the chain is
         // Strip(OFFSET) -> CheckIPHeader -> ..., so their bytes count from the
@@ -401,6 +431,29 @@ class RxCore {
         return 0;
     }
 
+    // ROUTES: StaticIPLookup's arguments in one string, "ADDR/MASK [GW] OUT"
+    // separated by commas (cp_ip_route, iproutetable.cc:35-60: GW may be "-";
+    // addr &= mask). Returns "" or what is wrong.
+    std::string parse_routes(std::string text) {
+        if (text.size() >= 2 && text.front() == '"' && text.back() == '"') text = text.substr(1, text.size() - 2);
+        for (const std::string &arg : split_conf(text)) {
+            std::istringstream ss(arg);
+            std::vector<std::string> w;
+            for (std::string x; ss >> x;) w.push_back(x);
+            const std::string bad = "'" + arg + "' should be 'ADDR/MASK [GATEWAY] OUTPUT'";
+            uint32_t addr, mask, gw = 0;
+            long port;
+            if (w.size() < 2 || w.size() > 3 || !parse_ip4_prefix(w[0], addr, mask)) return bad;
+            if (w.size() == 3 && w[1] != "-" && !parse_ip4(w[1], gw)) return bad;
+            if (!parse_int(w.back(), port)) return bad;
+            const uint32_t hm = __builtin_bswap32(mask);          // host order: a prefix is ones then zeros
+            if (hm & (~hm >> 1)) return "'" + w[0] + "': the mask is not a prefix";
+            if (port < 0 || port >= FCGPU_MAX_PORTS) return "'" + arg + "' bad OUTPUT";
+            _routes.push_back(fcgpu_route{addr & mask, gw, (uint8_t)__builtin_popcount(mask), (uint8_t)port, 0});
+        }
+        return std::string();
+    }
+
     int64_t timer_us() const { return _timer_us; }
     int error_output() const { return _error_output; }
     const fcgpu_cfg &device_cfg() const { return _cfg; }
@@ -434,6 +487,10 @@ class RxCore {
             rc = fcgpu_lb_hash_ring(_cfg.nports, (uint32_t)ring.size(), ring.data());
             if (rc == FCGPU_OK) rc = fcgpu_set_lb_table(_ctx, ring.data(), (uint32_t)ring.size());
             if (rc != FCGPU_OK) return err(errh, std::string("fcgpu_set_lb_table: ") + fcgpu_last_error(_ctx));
+        }
+        if (_cfg.classify == FCGPU_CLS_ROUTE) {
+            rc = fcgpu_set_routes(_ctx, _routes.data(), (uint32_t)_routes.size());
+            if (rc != FCGPU_OK) return err(errh, std::string("fcgpu_set_routes: ") + fcgpu_last_error(_ctx));
         }
         if (_flow_cap) {
             fcgpu_flow_config fc{_flow_mgr, _flow_cap, _flow_timeout, _flow_recycle_ms};
@@ -646,7 +703,27 @@ class RxCore {
         else if (h == "error") s << error;
         return s.str();
     }
+    // The `table` handler: the routes as IPRouteTable::dump_routes prints them
+    // (IPRoute::unparse with tabs, iproutetable.cc:62-82), in configuration
+    // order. Configuration only: the same on every thread's core.
+    std::string routes_text() const {
+        std::string s;
+        for (const fcgpu_route &r : _routes) {
+            const uint8_t *a = reinterpret_cast<const uint8_t *>(&r.addr), *g = reinterpret_cast<const uint8_t *>(&r.gw);
+            char pfx[24], gw[20];
+            snprintf(pfx, sizeof pfx, "%u.%u.%u.%u/%u", a[0], a[1], a[2], a[3], r.plen);
+            if (r.gw) snprintf(gw, sizeof gw, "%u.%u.%u.%u", g[0], g[1], g[2], g[3]);
+            else snprintf(gw, sizeof gw, "-");
+            s += pfx;
+            s += strlen(pfx) + 1 < 17 ? "\t\t" : "\t";
+            s += gw;
+            s += strlen(gw) + 1 < 9 ? "\t\t" : "\t";
+            s += std::to_string(r.port) + "\n";
+        }
+        return s;
+    }
     std::string read_handler(const std::string &h) {
+        if (h == "table") return routes_text();
         uint64_t c[FCGPU_NCOUNTERS];
         HostStats hs;
         std::string error;
@@ -1113,11 +1190,12 @@ class RxCore {
     // link the packets idx(b) .. idx(e-1) into PacketBatches of <= kMaxBatch
     template <class Idx, class Emit>
     void emit_run(Slot &s, uint32_t port, uint32_t b, uint32_t e, Idx idx, Emit &emit) {
-        const bool nomatch = port == _cfg.nports && _cfg.classify == FCGPU_CLS_PROGRAM;
+        const bool nomatch = port == _cfg.nports &&
+                             (_cfg.classify == FCGPU_CLS_PROGRAM || _cfg.classify == FCGPU_CLS_ROUTE);
         const bool last = port == _cfg.nports;
         if (nomatch || (last && _cfg.rewrite) || s.flowid || s.holes) {
             // the last list mixes invalid packets (output N) and packets no
-            // rule matched or SetIPChecksum rejected (killed); a full flow
+            // rule or route matched or SetIPChecksum rejected (killed); a full flow
             // table kills new flows. The rest keep input order.
             uint32_t w = 0;
             for (uint32_t j = b; j < e; ++j) {
@@ -1175,6 +1253,8 @@ class RxCore {
     fcgpu_ctx *_ctx = nullptr;
     bool _lb_direct = false;          // LB_MODE hash (IPFlowID), not hash_agg
     uint32_t _cst_buckets = 0;        // CST_BUCKETS (0: 100 per output)
+    std::vector<fcgpu_route> _routes; // ROUTES, addr &= mask applied
+    bool _routes_set = false;
     ParsedProgram _prog;
     uint32_t _prog_kind = FCGPU_PROG_IPFILTER;
     bool _prog_jit = true;

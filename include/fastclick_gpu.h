@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 25
+#define FCGPU_ABI_VERSION 26
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -117,6 +117,13 @@ extern "C" {
                                    (H&0xffff)) % buckets], H the hash_mode hash; the table
                                    (the reference's consistent-hash ring, :170-189) is set
                                    by fcgpu_set_lb_table */
+#define FCGPU_CLS_ROUTE      7  /* IPRouteTable::process (elements/ip/iproutetable.cc:152-169):
+                                   longest-prefix lookup of the DST_IP annotation in the
+                                   table set by fcgpu_set_routes; the route's output, its
+                                   gateway (if any) into the annotation; no route ->
+                                   FCGPU_R_NO_MATCH. The annotation is the header's ip_dst
+                                   word, as after GetIPAddress(16) (MARK_IP4, which sets
+                                   none itself, gets it too). IPv4 check modes only */
 
 /* l4_mode: a CheckUDPHeader / CheckTCPHeader after the IPv4 check (CHECK_IP4 or
  * MARK_IP4 only). The checksum covers the whole L4 segment, so with
@@ -526,6 +533,32 @@ int  fcgpu_set_lb_table(fcgpu_ctx *ctx, const uint8_t *table, uint32_t nbuckets)
  * constant_hash_agg ring, the table fcgpu_set_lb_table takes. Host-only (no
  * device, no context). */
 int  fcgpu_lb_hash_ring(uint32_t nsel, uint32_t size, uint8_t *out);
+
+/* The route table of FCGPU_CLS_ROUTE (StaticIPLookup's "ADDR/MASK [GW] OUT"
+ * routes): addr and gw are raw network-order words (gw 0 = no gateway: the
+ * packet keeps its DST_IP annotation), plen the prefix length (addr &= mask is
+ * applied, iproutetable.cc:41), port the output. fcgpu_set_routes replaces the
+ * context's table (n 0: an empty table, every packet has no route); a second
+ * route for one addr/plen ("conflict with existing route"), plen > 32, a port
+ * >= the configured nports (checked here and at every submission), more than
+ * 32767 distinct (gw, port) next hops, or a table that needs more than 32767
+ * 256-entry trie chunks is FCGPU_EINVAL and keeps the previous table, as an
+ * allocation failure does. On the device the table is a 16-8-8 multibit trie
+ * of 16-bit entries: 128 KiB + 512 B per chunk + 8 B per next
+ * hop. Synchronises the device before replacing a table. */
+typedef struct fcgpu_route {
+    uint32_t addr, gw;        /* raw network order                                        */
+    uint8_t  plen;            /* 0..32                                                    */
+    uint8_t  port;            /* output                                                   */
+    uint16_t reserved;
+} fcgpu_route;
+int  fcgpu_set_routes(fcgpu_ctx *ctx, const fcgpu_route *routes, uint32_t n);
+/* IPRouteTable::lookup_route over the same trie, walked as the device walks
+ * it: the output port of addr's longest matching prefix, or -1 (no route);
+ * *gw (may be NULL) = its gateway, 0 if none. nports 0: outputs unbounded.
+ * -2 for a route list fcgpu_set_routes would refuse (-1 is "no route";
+ * fcgpu_last_error(NULL) has the message). Host-only (no device, no context). */
+int  fcgpu_route_lookup(const fcgpu_route *routes, uint32_t n, uint32_t nports, uint32_t addr, uint32_t *gw);
 
 /* Flow table: the IPFlow5ID flow classification of
  * FlowIPManagerHMP (elements/research/flowipmanagerhmp.cc:96-126; the
