@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 26
+ABI_VERSION = 27
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -35,6 +35,7 @@ def reason_slot(r: int) -> int:
 CHECK_IP4, MARK_IP4, CHECK_AUTO, MARK_IP6 = 0, 1, 2, 3
 HASH_NONE, HASH_FLOWID, HASH_FLOW5ID = 0, 1, 2
 CLS_NONE, CLS_LB_HASH, CLS_HASH_IP, CLS_HASHSWITCH, CLS_PROGRAM, CLS_LB_CRC, CLS_LB_TABLE, CLS_ROUTE = range(8)
+CLS_ROUTE6 = 8
 PROG_IPFILTER, PROG_CLASSIFIER = 0, 1
 STEP_SHORT_YES = 1
 MAX_STEPS = 8192
@@ -206,6 +207,9 @@ FCGPU_SYMBOLS = {
     "fcgpu_lb_hash_ring": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
     "fcgpu_set_routes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "fcgpu_route_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fcgpu_set_routes6": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_route6_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint32)]),
+    "fcgpu_route6_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fcgpu_set_host_threads": (C.c_int, [C.c_void_p, C.c_uint32]),
     "fcgpu_span_submit": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                     C.POINTER(fcgpu_out)]),
@@ -344,6 +348,67 @@ def route_lookup(routes, addr, nports: int = 0):
     if port < -1:
         raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
     return port, gw.value
+
+
+def route6_dtype():
+    """numpy dtype of fcgpu_route6."""
+    import numpy as np
+    return np.dtype([("addr", "u1", 16), ("gw", "u1", 16), ("plen", "u1"), ("port", "u1"), ("reserved", "<u2")])
+
+
+def addr6(a) -> bytes:
+    """The 16 network-order bytes of an IPv6 address: a string (inet_pton),
+    16 bytes, or 0 / None for ::."""
+    import socket
+    if not a:
+        return bytes(16)
+    if isinstance(a, str):
+        return socket.inet_pton(socket.AF_INET6, a)
+    a = bytes(a)
+    if len(a) != 16:
+        raise ValueError("an IPv6 address is 16 bytes")
+    return a
+
+
+def routes6_array(routes):
+    """fcgpu_route6 records (a numpy structured array) from a sequence of
+    (addr, plen, gw, port): addr and gw strings or 16 bytes (addr6's forms),
+    gw 0 / None = no gateway. An array of that dtype passes through."""
+    import numpy as np
+    dt = route6_dtype()
+    if isinstance(routes, np.ndarray) and routes.dtype == dt:
+        return np.ascontiguousarray(routes)
+    out = np.zeros(len(routes), dt)
+    for k, (addr, plen, gw, port) in enumerate(routes):
+        if not (0 <= int(plen) <= 255 and 0 <= int(port) <= 255):
+            raise ValueError(f"route {k}: prefix length or output out of range")
+        out[k] = (np.frombuffer(addr6(addr), np.uint8), np.frombuffer(addr6(gw), np.uint8), plen, port, 0)
+    return out
+
+
+def route6_lookup(routes, addr, nports: int = 0):
+    """fcgpu_route6_lookup: (port, gateway id) of addr's longest matching
+    prefix in `routes` (routes6_array's forms), port -1 and id 0 without a
+    route. The trie is built and walked as on the device. Host-only. Raises
+    ValueError for a route list fcgpu_set_routes6 refuses."""
+    r = routes6_array(routes)
+    gw = C.c_uint32(0)
+    lib = load()
+    port = lib.fcgpu_route6_lookup(r.ctypes.data, len(r), nports, addr6(addr), C.byref(gw))
+    if port < -1:
+        raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
+    return port, gw.value
+
+
+def route6_stats(routes):
+    """fcgpu_route6_stats: (surviving chunks, longest walk in dependent loads)
+    of the trie built from `routes`."""
+    r = routes6_array(routes)
+    chunks, loads = C.c_uint32(0), C.c_uint32(0)
+    lib = load()
+    if lib.fcgpu_route6_stats(r.ctypes.data, len(r), C.byref(chunks), C.byref(loads)) != OK:
+        raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
+    return chunks.value, loads.value
 
 
 def default_cfg() -> fcgpu_cfg:
@@ -529,6 +594,12 @@ class Context:
         previous one."""
         r = routes_array(routes)
         self._chk(self.lib.fcgpu_set_routes(self.h, r.ctypes.data, len(r)), "fcgpu_set_routes")
+
+    def set_routes6(self, routes):
+        """The IPv6 route table of CLS_ROUTE6 (routes6_array's forms);
+        replaces the previous one."""
+        r = routes6_array(routes)
+        self._chk(self.lib.fcgpu_set_routes6(self.h, r.ctypes.data, len(r)), "fcgpu_set_routes6")
 
     def set_lb_table(self, table):
         """The bucket -> output table of CLS_LB_TABLE (uint8 sequence)."""

@@ -25,7 +25,7 @@ class fcclick_event(C.Structure):
 
 EV_BURST, EV_READ = 0, 1
 HANDLERS = ("count", "drops", "drop_details", "port_counts", "flow_count", "flow_count_fids", "flow_drops",
-            "gpu_errors", "gpu_retries", "error", "table")
+            "gpu_errors", "gpu_retries", "error", "table", "table6")
 
 
 class fcclick_result(C.Structure):
@@ -33,7 +33,7 @@ class fcclick_result(C.Structure):
                 ("out_dst", C.c_void_p), ("out_len", C.c_void_p), ("out_nh", C.c_void_p),
                 ("out_batches", C.c_void_p), ("handlers", C.c_char_p), ("handlers_cap", C.c_size_t),
                 ("out_paint", C.c_void_p), ("out_flow", C.c_void_p), ("out_ip8", C.c_void_p),
-                ("out_parked", C.c_void_p), ("out_batch", C.c_void_p)]
+                ("out_parked", C.c_void_p), ("out_batch", C.c_void_p), ("out_dst6", C.c_void_p)]
 
 
 def load():
@@ -186,6 +186,7 @@ class _Run:
                                                      ("dst", np.uint32), ("len", np.uint32), ("nh", np.int32),
                                                      ("paint", np.uint8), ("flow", np.uint32),
                                                      ("ip8", np.uint32), ("batch", np.uint32))}
+        self.out["dst6"] = np.zeros((n, 16), np.uint8)
         self.nb = np.zeros(1, np.uint32)
         self.parked = np.zeros(1, np.uint32)
         self.hbuf = C.create_string_buffer(4096)
@@ -194,7 +195,7 @@ class _Run:
                                   o["dst"].ctypes.data, o["len"].ctypes.data, o["nh"].ctypes.data,
                                   self.nb.ctypes.data, C.cast(self.hbuf, C.c_char_p), 4096,
                                   o["paint"].ctypes.data, o["flow"].ctypes.data, o["ip8"].ctypes.data,
-                                  self.parked.ctypes.data, o["batch"].ctypes.data)
+                                  self.parked.ctypes.data, o["batch"].ctypes.data, o["dst6"].ctypes.data)
         self.err = C.create_string_buffer(512)
 
     def finish(self, rc: int, allow_error: bool) -> dict:

@@ -166,6 +166,7 @@ void fcgpu_close(fcgpu_ctx *c) {
         hipFree(c->d_crc);
         hipFree(c->d_lbtab);
         hipFree(c->d_routes);
+        hipFree(c->d_routes6);
         hipFree(c->d_verdict);
         hipFree(c->d_arena);
         hipFree(c->d_desc);
@@ -260,7 +261,9 @@ int fcgpu_configure(fcgpu_ctx *c, const fcgpu_cfg *cfg) {
     const bool ip4mode = cfg->check_mode == FCGPU_CHECK_IP4 || cfg->check_mode == FCGPU_MARK_IP4;
     if (cfg->vlan_ethertype > 0xffff) return fail(c, FCGPU_EINVAL, "bad vlan_ethertype");
     if (cfg->hash_mode > FCGPU_HASH_FLOW5ID) return fail(c, FCGPU_EINVAL, "bad hash_mode");
-    if (cfg->classify > FCGPU_CLS_ROUTE) return fail(c, FCGPU_EINVAL, "bad classify mode");
+    if (cfg->classify > FCGPU_CLS_ROUTE6) return fail(c, FCGPU_EINVAL, "bad classify mode");
+    if (cfg->classify == FCGPU_CLS_ROUTE6 && cfg->check_mode != FCGPU_CHECK_AUTO && cfg->check_mode != FCGPU_MARK_IP6)
+        return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE6 looks up the header's ip6_dst: CHECK_AUTO and MARK_IP6 only");
     if (cfg->classify == FCGPU_CLS_ROUTE && !ip4mode)
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE looks up the IPv4 DST_IP annotation: IPv4 check modes only");
     if (cfg->classify == FCGPU_CLS_LB_CRC && !(cfg->check_mode == FCGPU_CHECK_IP4 || cfg->check_mode == FCGPU_MARK_IP4))
@@ -330,9 +333,12 @@ int fcgpu_configure(fcgpu_ctx *c, const fcgpu_cfg *cfg) {
     d.lb_tab = cfg->classify == FCGPU_CLS_LB_TABLE ? c->d_lbtab : nullptr;
     d.lb_tab_n = c->lbtab_n;
     d.lb_tab_magic = c->lbtab_n > 1 ? (uint32_t)((((uint64_t)1 << 32) + c->lbtab_n - 1) / c->lbtab_n) : 0u;
-    d.rt = cfg->classify == FCGPU_CLS_ROUTE ? reinterpret_cast<const uint16_t *>(c->d_routes) : nullptr;
+    d.rt = c->dev_rt();
     d.rt_hop_off = c->rt_hop_off;
     d.rt_nhops = c->rt_nhops;
+    d.rt6 = c->dev_rt6();
+    d.rt6_hop_off = c->rt6_hop_off;
+    d.rt6_nhops = c->rt6_nhops;
     d.prog = c->d_prog;
     d.prog_n = c->prog_n;
     d.prog_q = c->prog_q;

@@ -60,6 +60,9 @@ struct DevCfg {
     const uint16_t *rt;       // FCGPU_CLS_ROUTE: l0[65536], then the chunk pool (host/route_table.hh)
     uint32_t rt_hop_off;      // byte offset of the next hops ({gw, port}, 8 B each) from rt
     uint32_t rt_nhops;        // next hops, entry 0 (no route) included
+    const uint32_t *rt6;      // FCGPU_CLS_ROUTE6: root[65536], then 1040-B chunks (host/route6_table.hh)
+    uint32_t rt6_hop_off;     // byte offset of its next hops ({gw id, port}, 8 B each) from rt6
+    uint32_t rt6_nhops;       // next hops, entry 0 (no route) included
 };
 
 // Device step: x = (u16)offset | flags << 16, y = value, z = mask,
@@ -301,6 +304,71 @@ __device__ __forceinline__ uint32_t route_apply(const DevCfg &c, uint2 hop, fcgp
     return hop.y;
 }
 
+// ---- FCGPU_CLS_ROUTE6: LookupIP6Route over the path-compressed trie ---------
+// (host/route6_table.hh has the structure and its builder)
+// k[0..3]: the header's ip6_dst as four little-endian words, in registers.
+// The root load depends only on k[0] (address bytes 0..1: in range for any
+// word), so the callers issue it as soon as the frame is known to be IPv6.
+constexpr uint32_t kRt6RootBytes = 65536 * 4;
+constexpr uint32_t kRt6ChunkBytes = 1040;    // uint4 header + 256 entries
+__device__ __forceinline__ uint32_t route6_probe(const DevCfg &c, uint32_t k0) {
+    return c.rt6[__builtin_bswap32(k0) >> 16];
+}
+// bm: one bit per address byte; its nibble j spread to a byte mask over
+// little-endian word j of the address (the four shifted copies do not overlap)
+__device__ __forceinline__ uint32_t rt6_mask(uint32_t bm, int j) {
+    return ((((bm >> (4 * j)) & 15u) * 0x00204081u) & 0x01010101u) * 0xffu;
+}
+// e0: route6_probe's entry. Per chunk on the path the header (only when bytes
+// were skipped) and the entry at the index byte are issued together -- the
+// parent entry gives both addresses -- so a chunk costs one round trip. The
+// skipped bytes sit in the header at their own address positions: the compare
+// is four masked xors of registers. A mismatch ends at the chunk's default
+// leaf. Returns the next hop {gw id, port}, from LDS or global memory as
+// route_walk does (two branches, the vector-memory count drained before the
+// join: lb_table_port's comment).
+__device__ __forceinline__ uint2 route6_walk(const DevCfg &c, const uint4 *dyn, uint32_t k0, uint32_t k1, uint32_t k2,
+                                             uint32_t k3, uint32_t e0) {
+    // the key by value, and its index byte by a 64-bit shift of one half: an
+    // array indexed by the depth would live in scratch
+    const uint64_t klo = k0 | (uint64_t)k1 << 32, khi = k2 | (uint64_t)k3 << 32;
+    const uint8_t *pool = reinterpret_cast<const uint8_t *>(c.rt6) + kRt6RootBytes;
+    uint32_t e = e0, d = 2;
+    while (e & 0x80000000u) {                  // at most 14 chunks: d grows by >= 1, ends at byte 15
+        const uint32_t skip = (e >> 27) & 15u;
+        const uint8_t *ch = pool + (size_t)(e & 0x07ffffffu) * kRt6ChunkBytes;
+        const uint32_t at = (d + skip) & 15u;  // the index byte's position
+        const uint32_t idx = (uint32_t)((at < 8 ? klo : khi) >> (8 * (at & 7u))) & 0xffu;
+        uint4 hd = make_uint4(0, 0, 0, 0);
+        if (skip) hd = *reinterpret_cast<const uint4 *>(ch);
+        const uint32_t ne = reinterpret_cast<const uint32_t *>(ch + 16)[idx];
+        uint32_t diff = 0;
+        if (skip) {
+            const uint32_t bm = ((1u << skip) - 1u) << d;      // bytes [d, d + skip), all below 15
+            diff = ((hd.x ^ k0) & rt6_mask(bm, 0)) | ((hd.y ^ k1) & rt6_mask(bm, 1)) |
+                   ((hd.z ^ k2) & rt6_mask(bm, 2)) | ((hd.w ^ k3) & rt6_mask(bm, 3));
+        }
+        e = diff ? (hd.x & 0xffffu) : ne;
+        d = at + 1;
+    }
+    if (dyn) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): e is needed here anyway
+        return reinterpret_cast<const uint2 *>(dyn)[e];
+    }
+    const uint2 h = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(c.rt6) + c.rt6_hop_off)[e];
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    return h;
+}
+// An IPv4 packet under FCGPU_CLS_ROUTE6 (CHECK_AUTO, dual stack): the IPv4
+// table if one is set (wave-uniform), its next hops from global memory -- the
+// dynamic LDS slot holds the IPv6 ones -- else no route.
+__device__ __forceinline__ uint32_t route64_probe(const DevCfg &c, uint32_t dst_raw) {
+    return c.rt ? route_probe(c, dst_raw) : 0u;
+}
+__device__ __forceinline__ uint2 route64_walk(const DevCfg &c, uint32_t dst_raw, uint32_t e0) {
+    return c.rt ? route_walk(c, nullptr, dst_raw, e0) : make_uint2(0u, kRtNoPort);
+}
+
 // rte_hash_crc_4byte(data, crc) (DPDK rte_hash_crc.h: _mm_crc32_u32(crc, data)):
 // CRC32-C, reflected polynomial 0x82F63B78, no inversion -- a reflected CRC
 // takes the 32-bit word at once (xor) and shifts it through bit by bit.
@@ -458,9 +526,14 @@ __host__ __device__ inline bool tab_in_lds(const DevCfg &c) {
 __host__ __device__ inline bool hops_in_lds(const DevCfg &c) {
     return c.classify == FCGPU_CLS_ROUTE && c.rt && c.rt_nhops * 8u <= kTabLdsBytes;
 }
+// FCGPU_CLS_ROUTE6: the IPv6 next hops likewise (a dual-stack IPv4 table's stay in global memory)
+__host__ __device__ inline bool hops6_in_lds(const DevCfg &c) {
+    return c.classify == FCGPU_CLS_ROUTE6 && c.rt6 && c.rt6_nhops * 8u <= kTabLdsBytes;
+}
 inline size_t prog_lds_bytes(const DevCfg &c) {
     return prog_in_lds(c) ? sizeof(uint4) * c.prog_q : crc_in_lds(c) ? sizeof(uint4) * kCrcTabQ
-         : tab_in_lds(c) ? (c.lb_tab_n + 15u) & ~15u : hops_in_lds(c) ? (c.rt_nhops * 8u + 15u) & ~15u : 0;
+         : tab_in_lds(c) ? (c.lb_tab_n + 15u) & ~15u : hops_in_lds(c) ? (c.rt_nhops * 8u + 15u) & ~15u
+         : hops6_in_lds(c) ? (c.rt6_nhops * 8u + 15u) & ~15u : 0;
 }
 #ifdef FCGPU_JIT_PROGRAM
 // The installed program compiled to straight-line code (fcgpu_program_jit,
@@ -556,13 +629,14 @@ __device__ __forceinline__ uint32_t check_ip6(const DevCfg &c, const FrameView &
     return FCGPU_R_OK;
 }
 
-template <int CM, bool CK, bool PROG, bool ROUTE = false>
+template <int CM, bool CK, bool PROG, int ROUTE = 0>
 __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView &f, uint32_t len,
                                                PktResult &r, const uint4 *sprog) {
     fcgpu_anno &an = r.an;
     uint32_t o = (uint32_t)c.offset;
     uint32_t h[5] = {0, 0, 0, 0, 0};
     bool v6 = false;
+    uint32_t k6[4] = {0, 0, 0, 0}, rt0 = 0;   // FCGPU_CLS_ROUTE6: ip6_dst and the trie's root entry
     r.hash = 0;
     if (CM == FCGPU_CHECK_AUTO) {
         // StripEtherVLANHeader::simple_action (stripethervlanheader.cc:48-61)
@@ -580,6 +654,10 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
         }
         an.nh = (uint16_t)o;                       // the pull() StripEtherVLANHeader did
         v6 = ((int)(len - o) >= 1) && ((f.rd8(o) >> 4) == 6);
+        if (ROUTE == 2 && v6 && (int)(len - o) >= 40) {   // the root load runs under check_ip6's chain
+            f.run<4>(o + 24, k6);
+            rt0 = route6_probe(c, k6[0]);
+        }
         r.reason = v6 ? check_ip6(c, f, len, o, an) : check_ip4<CK>(c, f, len, o, h, an);
     } else if (CM == FCGPU_MARK_IP6) {
         // MarkIP6Header::simple_action (markip6header.cc:43-48): set_ip6_header(o, 40)
@@ -588,6 +666,10 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
         an.length = (uint16_t)len;
         an.ipver = 6;
         v6 = true;
+        if (ROUTE == 2) {   // GetIP6Address(24), as the reference reads it: the window or the arena beyond
+            f.run<4>(o + 24, k6);
+            rt0 = route6_probe(c, k6[0]);
+        }
         r.reason = FCGPU_R_OK;
     } else if (CM == FCGPU_MARK_IP4) {
         // MarkIPHeader::simple_action (markipheader.cc:43-48)
@@ -621,7 +703,12 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
         }
     }
     r.hash = hv;
-    if (ROUTE) {   // FCGPU_CLS_ROUTE (IPv4 check modes): the general path probes once the checks are done
+    if (ROUTE == 2) {   // FCGPU_CLS_ROUTE6; an IPv4 packet (CHECK_AUTO) keeps check_ip4's dst_ip or gets the gateway
+        const uint2 hop = v6 ? route6_walk(c, sprog, k6[0], k6[1], k6[2], k6[3], rt0) : route64_walk(c, h[4], route64_probe(c, h[4]));
+        r.port = route_apply(c, hop, an, r.reason);
+        return;
+    }
+    if (ROUTE == 1) {   // FCGPU_CLS_ROUTE (IPv4 check modes): the general path probes once the checks are done
         an.dst_ip = h[4];   // the chain's GetIPAddress(16): MarkIPHeader alone leaves the annotation unset
         r.port = route_apply(c, route_walk(c, sprog, h[4], route_probe(c, h[4])), an, r.reason);
         return;
@@ -662,7 +749,7 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
 // branches except the (wave-uniform) configuration. Returns false when this
 // lane needs the general path (options, header beyond the window, hash modes
 // or classifiers it does not cover); the caller then runs process_packet.
-template <bool CK, bool PROG, bool ROUTE = false>
+template <bool CK, bool PROG, int ROUTE = 0>
 __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, uint32_t len, uint32_t o, PktResult &r,
                                          const uint4 *sprog) {
     const uint32_t x = f.shift + o, a = x & ~3u, sh = x & 3u;
@@ -771,7 +858,7 @@ __device__ __forceinline__ uint32_t win32(const FrameView &f, uint32_t b) {
 // its version's result: CheckIPHeader as ip4_fast, CheckIP6Header
 // (checkip6header.cc:105-150) and IP6FlowID::hashcode (ip6flowid.hh:220-230)
 // for the IPv6 header and first L4 word; same outputs as process_packet.
-template <bool CK, bool PROG>
+template <bool CK, bool PROG, int ROUTE = 0>
 __device__ __forceinline__ bool auto_fast(const DevCfg &c, const FrameView &f, uint32_t len, PktResult &r,
                                           const uint4 *sprog) {
     const uint32_t o = (uint32_t)c.offset;
@@ -793,6 +880,10 @@ __device__ __forceinline__ bool auto_fast(const DevCfg &c, const FrameView &f, u
     for (int j = 0; j < 11; ++j) h[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
     const uint32_t plen = len - x;
     const bool v6 = (int)plen >= 1 && (h[0] & 0xf0) == 0x60;
+    // FCGPU_CLS_ROUTE6: the first entry of the lane's trie, loaded while the
+    // checks run (lanes that decline below loaded an in-range entry for nothing)
+    uint32_t rt0 = 0;
+    if (ROUTE == 2) rt0 = v6 ? route6_probe(c, h[6]) : route64_probe(c, h[4]);
     // classifiers the straight line covers (wave-uniform)
     const bool prog = PROG && c.classify == FCGPU_CLS_PROGRAM;
     // byte sums (hash_ip = HashSwitch(26, 8)) over frame bytes inside the window
@@ -800,9 +891,10 @@ __device__ __forceinline__ bool auto_fast(const DevCfg &c, const FrameView &f, u
     const uint32_t bo = c.classify == FCGPU_CLS_HASH_IP ? 26u : (uint32_t)c.hs_offset;
     const uint32_t bl = c.classify == FCGPU_CLS_HASH_IP ? 8u : (uint32_t)c.hs_length;
     const bool bwin = !bsum || f.shift + bo + bl <= (uint32_t)kWin;
-    const bool cls4 = c.classify == FCGPU_CLS_LB_HASH || c.classify == FCGPU_CLS_LB_CRC ||
+    const bool cls4 = ROUTE == 2 || c.classify == FCGPU_CLS_LB_HASH || c.classify == FCGPU_CLS_LB_CRC ||
                       c.classify == FCGPU_CLS_LB_TABLE || c.classify == FCGPU_CLS_NONE || prog || bsum;
-    const bool cls6 = c.classify == FCGPU_CLS_LB_HASH || c.classify == FCGPU_CLS_LB_TABLE || prog || bsum;
+    const bool cls6 = ROUTE == 2 || c.classify == FCGPU_CLS_LB_HASH || c.classify == FCGPU_CLS_LB_TABLE || prog ||
+                      bsum;
     // CheckIPHeader::valid's reason chain as predicates (ip4_fast)
     const uint32_t b0 = h[0] & 0xff, hlen = (b0 & 15) << 2, L = bswap16(h[0] >> 16);
     const bool tiny = (int)plen < 20, badv = (b0 >> 4) != 4, badhl = hlen < 20;
@@ -852,7 +944,9 @@ __device__ __forceinline__ bool auto_fast(const DevCfg &c, const FrameView &f, u
         if (c.hash_mode == FCGPU_HASH_FLOW5ID && !v6) hv ^= (h[2] >> 8) & 0xff;
     }
     uint32_t port = 0;
-    if (c.classify == FCGPU_CLS_LB_HASH) {
+    if (ROUTE == 2) {
+        // below, with the annotation the gateway goes into
+    } else if (c.classify == FCGPU_CLS_LB_HASH) {
         port = (uint32_t)lb_port(hv, c.nports, c.lb_magic);
     } else if (c.classify == FCGPU_CLS_LB_CRC) {   // IPv4 lanes only (cls6)
         const bool first = (bswap16(h[1] >> 16) & 0x1fff) == 0;
@@ -877,6 +971,15 @@ __device__ __forceinline__ bool auto_fast(const DevCfg &c, const FrameView &f, u
     if (prog && ok) {
         port = run_program(c, f, an, sprog);
         if (port >= c.nports) r.reason = FCGPU_R_NO_MATCH;
+    }
+    if (ROUTE == 2 && ok) {
+        uint2 hop;
+        if (v6) {
+            hop = route6_walk(c, sprog, h[6], h[7], h[8], h[9], rt0);
+        } else {
+            hop = route64_walk(c, h[4], rt0);
+        }
+        port = route_apply(c, hop, an, r.reason);
     }
     r.port = ok && port < c.nports ? port : c.nports;
     return true;
@@ -1393,7 +1496,7 @@ __device__ __forceinline__ RxView rx_view(const RxArgs &A) {
 // classify; per-wave histogram by ballots; counters by sharded atomics;
 // optionally the tile's stable per-output partition (CLASSIFY_EACH_PACKET on a
 // 256-packet PacketBatch).
-template <int CM, bool CK, int PART, bool PROG, bool L4, bool FAST, bool FLOW, bool ROUTE = false>
+template <int CM, bool CK, int PART, bool PROG, bool L4, bool FAST, bool FLOW, int ROUTE = 0>
 __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const FlowArgs &FL, uint32_t tile, uint2 d,
                                         const uint8_t *wl,
                                         uint32_t (*s_cnt)[kMaxBins], const uint4 *sprog) {
@@ -1420,11 +1523,11 @@ __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const 
         }
     } else if (FAST && CM == FCGPU_CHECK_AUTO) {
         bool done = !live;
-        if (live) done = auto_fast<CK, PROG>(A.cfg, f, d.y, r, sprog);
+        if (live) done = auto_fast<CK, PROG, ROUTE>(A.cfg, f, d.y, r, sprog);
         if (__ballot(!done)) {
             if (!done) {
                 r.an = fcgpu_anno{};
-                process_packet<CM, CK, PROG>(A.cfg, f, d.y, r, sprog);
+                process_packet<CM, CK, PROG, ROUTE>(A.cfg, f, d.y, r, sprog);
             }
         }
     } else if (live) {
@@ -1552,11 +1655,12 @@ struct RxLaunch {
     RxJob job[kMaxFuse];
 };
 
-// ROUTE: the FCGPU_CLS_ROUTE classifier, compiled only into the kernels
-// launched for it (IPv4 check modes), as PROG is for decision programs: the
-// other instances keep their classify chain as it was.
+// ROUTE: 1 = the FCGPU_CLS_ROUTE classifier (IPv4 check modes), 2 =
+// FCGPU_CLS_ROUTE6 (CHECK_AUTO, MARK_IP6), each compiled only into the kernels
+// launched for it, as PROG is for decision programs: the other instances keep
+// their classify chain as it was.
 template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false,
-          bool FAST = (CM == FCGPU_CHECK_IP4 || CM == FCGPU_CHECK_AUTO), bool ROUTE = false>
+          bool FAST = (CM == FCGPU_CHECK_IP4 || CM == FCGPU_CHECK_AUTO), int ROUTE = 0>
 __global__ __launch_bounds__(kTile, 8) void k_rx(RxLaunch L) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[4 * kWave * kWin];
     __shared__ uint32_t s_cnt[4][kMaxBins];
@@ -1621,10 +1725,13 @@ __global__ __launch_bounds__(kTile, 8) void k_rx(RxLaunch L) {
     if (tab_lds && threadIdx.x * 16u < A.cfg.lb_tab_n)
         s_prog[threadIdx.x] = reinterpret_cast<const uint4 *>(A.cfg.lb_tab)[threadIdx.x];
     // next hops of a route table: two per thread, the device image is padded to 16 B
-    const bool hop_lds = ROUTE && hops_in_lds(A.cfg);         // block-uniform
-    if (hop_lds && threadIdx.x * 2u < A.cfg.rt_nhops)
+    const bool hop_lds = ROUTE == 1 ? hops_in_lds(A.cfg) : ROUTE == 2 ? hops6_in_lds(A.cfg) : false;   // block-uniform
+    if (ROUTE == 1 && hop_lds && threadIdx.x * 2u < A.cfg.rt_nhops)
         s_prog[threadIdx.x] = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(A.cfg.rt) +
                                                               A.cfg.rt_hop_off)[threadIdx.x];
+    if (ROUTE == 2 && hop_lds && threadIdx.x * 2u < A.cfg.rt6_nhops)
+        s_prog[threadIdx.x] = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(A.cfg.rt6) +
+                                                              A.cfg.rt6_hop_off)[threadIdx.x];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (every wave copying the whole table by LDS-DMA instead, with no block
     // barrier, measured the same: profiles/r05_lb/nobarrier_*)

@@ -224,6 +224,18 @@ struct fcgpu_ctx {
     uint32_t rt_hop_off = 0, rt_nhops = 0;    // its next hops: byte offset, count (0: no table)
     uint32_t rt_max_port = 0;                 // largest output of any route
     uint64_t rt_key = 0;                      // hash of the image (0: none)
+    uint8_t *d_routes6 = nullptr;             // CLS_ROUTE6 trie image (fcgpu_set_routes6, host/route6_table.hh)
+    uint32_t rt6_hop_off = 0, rt6_nhops = 0;  // its next hops: byte offset, count (0: no table)
+    uint32_t rt6_max_port = 0;                // largest output of any route
+    uint64_t rt6_key = 0;                     // hash of the image (0: none)
+    // the IPv4 table serves CLS_ROUTE and, as the IPv4 half of a dual stack, CLS_ROUTE6
+    const uint16_t *dev_rt() const {
+        return cfg.classify == FCGPU_CLS_ROUTE || cfg.classify == FCGPU_CLS_ROUTE6
+                   ? reinterpret_cast<const uint16_t *>(d_routes) : nullptr;
+    }
+    const uint32_t *dev_rt6() const {
+        return cfg.classify == FCGPU_CLS_ROUTE6 ? reinterpret_cast<const uint32_t *>(d_routes6) : nullptr;
+    }
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)

@@ -18,7 +18,7 @@ static_assert(kCrcTabQ <= kTile, "k_rx copies the CRC tables with one uint4 per 
 // L: one batch (njobs 1, grid = its tiles) or several fused ones (grid =
 // their tiles end to end).
 
-template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false, bool ROUTE = false>
+template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false, int ROUTE = 0>
 static void launch_rx(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
                       fcgpu_ctx *jc) {
     if (PROG && jc) {   // the program compiled to code, when the context has it
@@ -43,7 +43,7 @@ static void launch_rx(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_
 
 // IPv4 check modes: L4 (CheckUDPHeader/CheckTCPHeader) and the flow table
 // exist only there (fcgpu_configure / fcgpu_process reject them with CHECK_AUTO).
-template <int CM, bool CK, int PART, bool PROG, bool ROUTE = false>
+template <int CM, bool CK, int PART, bool PROG, int ROUTE = 0>
 static void launch_rx_ip4(const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1, fcgpu_ctx *jc) {
     const bool l4 = L.A.cfg.l4_mode != FCGPU_L4_NONE, flow = L.A.fl.slots != nullptr;
     if (flow) {
@@ -61,10 +61,23 @@ template <int PART>
 static hipError_t launch_rx_route(uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0,
                                   hipEvent_t e1) {
     if (!L.A.cfg.rt || !L.A.cfg.rt_nhops) return hipErrorInvalidValue;
-    if (cm == FCGPU_MARK_IP4) launch_rx_ip4<FCGPU_MARK_IP4, false, PART, false, true>(L, grid, s, e0, e1, nullptr);
+    if (cm == FCGPU_MARK_IP4) launch_rx_ip4<FCGPU_MARK_IP4, false, PART, false, 1>(L, grid, s, e0, e1, nullptr);
     else if (cm != FCGPU_CHECK_IP4) return hipErrorInvalidValue;
-    else if (ck) launch_rx_ip4<FCGPU_CHECK_IP4, true, PART, false, true>(L, grid, s, e0, e1, nullptr);
-    else launch_rx_ip4<FCGPU_CHECK_IP4, false, PART, false, true>(L, grid, s, e0, e1, nullptr);
+    else if (ck) launch_rx_ip4<FCGPU_CHECK_IP4, true, PART, false, 1>(L, grid, s, e0, e1, nullptr);
+    else launch_rx_ip4<FCGPU_CHECK_IP4, false, PART, false, 1>(L, grid, s, e0, e1, nullptr);
+    return hipSuccess;
+}
+
+// FCGPU_CLS_ROUTE6: CHECK_AUTO (checksum on and off) and MARK_IP6, which have
+// neither the L4 checks nor the flow table; an IPv4 table is optional (dual stack).
+template <int PART>
+static hipError_t launch_rx_route6(uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s,
+                                   hipEvent_t e0, hipEvent_t e1) {
+    if (!L.A.cfg.rt6 || !L.A.cfg.rt6_nhops) return hipErrorInvalidValue;
+    if (cm == FCGPU_MARK_IP6) launch_rx<FCGPU_MARK_IP6, false, PART, false, false, false, 2>(L, grid, s, e0, e1, nullptr);
+    else if (cm != FCGPU_CHECK_AUTO) return hipErrorInvalidValue;
+    else if (ck) launch_rx<FCGPU_CHECK_AUTO, true, PART, false, false, false, 2>(L, grid, s, e0, e1, nullptr);
+    else launch_rx<FCGPU_CHECK_AUTO, false, PART, false, false, false, 2>(L, grid, s, e0, e1, nullptr);
     return hipSuccess;
 }
 
@@ -124,6 +137,10 @@ hipError_t launch_rx_any(int part, uint32_t cm, bool ck, const RxLaunch &L, uint
         return part == kPartTile     ? launch_rx_route<kPartTile>(cm, ck, L, grid, s, e0, e1)
                : part == kPartGlobal ? launch_rx_route<kPartGlobal>(cm, ck, L, grid, s, e0, e1)
                                      : launch_rx_route<kPartNone>(cm, ck, L, grid, s, e0, e1);
+    if (L.A.cfg.classify == FCGPU_CLS_ROUTE6)
+        return part == kPartTile     ? launch_rx_route6<kPartTile>(cm, ck, L, grid, s, e0, e1)
+               : part == kPartGlobal ? launch_rx_route6<kPartGlobal>(cm, ck, L, grid, s, e0, e1)
+                                     : launch_rx_route6<kPartNone>(cm, ck, L, grid, s, e0, e1);
     if (L.A.cfg.classify == FCGPU_CLS_PROGRAM) launch_rx_prog<true>(part, cm, ck, L, grid, s, e0, e1, jc);
     else launch_rx_prog<false>(part, cm, ck, L, grid, s, e0, e1, jc);
     return hipSuccess;

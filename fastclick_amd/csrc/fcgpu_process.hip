@@ -28,6 +28,9 @@ int check_process(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, 
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_LB_TABLE without fcgpu_set_lb_table of outputs < nports");
     if (c->cfg.classify == FCGPU_CLS_ROUTE && (!c->d_routes || c->rt_max_port >= c->cfg.nports))
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE without fcgpu_set_routes of outputs < nports");
+    if (c->cfg.classify == FCGPU_CLS_ROUTE6 &&
+        (!c->d_routes6 || c->rt6_max_port >= c->cfg.nports || (c->d_routes && c->rt_max_port >= c->cfg.nports)))
+        return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE6 without fcgpu_set_routes6, or a route table with outputs >= nports");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n && (!d_arena || !d_desc)) return fail(c, FCGPU_EINVAL, "null arena/desc");
     if (o->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");

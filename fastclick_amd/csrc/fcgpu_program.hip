@@ -2,9 +2,10 @@
 // IPClassifier / Classifier): upload with jump tables
 // (build_tables), compiled programs (fcgpu_program_jit, hiprtc through
 // prog_jit.hh), the LoadBalancer hash tables (FCGPU_CLS_LB_TABLE) and the
-// route table (FCGPU_CLS_ROUTE).
+// route tables (FCGPU_CLS_ROUTE, FCGPU_CLS_ROUTE6).
 #include "fcgpu_internal.hh"
 #include "host/route_table.hh"
+#include "host/route6_table.hh"
 #include "jit_sources.inc"   // kJitDeviceHh, kJitAbiH (fastclick_amd/build.py)
 
 using namespace fcgpu;
@@ -307,7 +308,7 @@ int fcgpu_set_routes(fcgpu_ctx *c, const fcgpu_route *routes, uint32_t n) {
     for (uint8_t b : img) key = (key ^ b) * 1099511628211ull;
     c->rt_key = (key ^ img.size()) | 1;
     DevCfg &d = c->dcfg;
-    d.rt = c->cfg.classify == FCGPU_CLS_ROUTE ? reinterpret_cast<const uint16_t *>(c->d_routes) : nullptr;
+    d.rt = c->dev_rt();
     d.rt_hop_off = hop_off;
     d.rt_nhops = c->rt_nhops;
     return FCGPU_OK;
@@ -321,6 +322,64 @@ int fcgpu_route_lookup(const fcgpu_route *routes, uint32_t n, uint32_t nports, u
         return -2;
     }
     return fcroute::lookup(t, addr, gw);
+}
+
+// FCGPU_CLS_ROUTE6: the path-compressed trie of host/route6_table.hh, one
+// image; same contract as fcgpu_set_routes.
+int fcgpu_set_routes6(fcgpu_ctx *c, const fcgpu_route6 *routes, uint32_t n) {
+    if (!c) return FCGPU_EINVAL;
+    if (!routes && n) return fail(c, FCGPU_EINVAL, "fcgpu_set_routes6: null routes");
+    if (agg_queued(c)) return fail(c, FCGPU_EINVAL, "fcgpu_set_routes6: a queued span submission is not waited for");
+    fcroute6::Table t;
+    std::string why;
+    if (fcroute6::build(routes, n, c->configured ? c->cfg.nports : 0, t, why) != FCGPU_OK)
+        return fail(c, FCGPU_EINVAL, "fcgpu_set_routes6: " + why);
+    uint32_t hop_off = 0;
+    const std::vector<uint8_t> img = fcroute6::image(t, hop_off);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    // uploaded before the old table is freed: a failure leaves it intact
+    uint8_t *nt = nullptr;
+    if (int rc = alloc_or_fail(c, "fcgpu_set_routes6", {dev_buf(nt, img.size())})) return rc;
+    if (hipError_t e = hipMemcpy(nt, img.data(), img.size(), hipMemcpyHostToDevice)) {
+        (void)hipFree(nt);
+        return fail(c, FCGPU_ERUNTIME, std::string("fcgpu_set_routes6 upload: ") + hipGetErrorString(e));
+    }
+    hipFree(c->d_routes6);
+    c->d_routes6 = nt;
+    c->rt6_hop_off = hop_off;
+    c->rt6_nhops = (uint32_t)t.hops.size();
+    c->rt6_max_port = t.max_port;
+    uint64_t key = 1469598103934665603ull;
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(img.data());      // the image is a multiple of 16 B
+    for (size_t k = 0; k < img.size() / 8; ++k) key = (key ^ w[k]) * 1099511628211ull;
+    c->rt6_key = (key ^ img.size()) | 1;
+    DevCfg &d = c->dcfg;
+    d.rt6 = c->dev_rt6();
+    d.rt6_hop_off = hop_off;
+    d.rt6_nhops = c->rt6_nhops;
+    return FCGPU_OK;
+}
+
+int fcgpu_route6_lookup(const fcgpu_route6 *routes, uint32_t n, uint32_t nports, const uint8_t addr[16],
+                        uint32_t *gw_id) {
+    fcroute6::Table t;
+    std::string why;
+    if ((!routes && n) || !addr || fcroute6::build(routes, n, nports, t, why) != FCGPU_OK) {
+        fail(nullptr, FCGPU_EINVAL, "fcgpu_route6_lookup: " + (why.empty() ? std::string("null argument") : why));
+        return -2;
+    }
+    return fcroute6::lookup(t, addr, gw_id);
+}
+
+int fcgpu_route6_stats(const fcgpu_route6 *routes, uint32_t n, uint32_t *chunks, uint32_t *max_loads) {
+    fcroute6::Table t;
+    std::string why;
+    if ((!routes && n) || fcroute6::build(routes, n, 0, t, why) != FCGPU_OK)
+        return fail(nullptr, FCGPU_EINVAL, "fcgpu_route6_stats: " + (why.empty() ? std::string("null routes") : why));
+    if (chunks) *chunks = t.nchunks();
+    if (max_loads) *max_loads = t.max_loads;
+    return FCGPU_OK;
 }
 
 int fcgpu_program_jit(fcgpu_ctx *c, int enable) {

@@ -117,6 +117,7 @@ static bool agg_compatible(const AggItem &a, const AggItem &b) {
     x.crc_tab = y.crc_tab = nullptr;
     x.lb_tab = y.lb_tab = nullptr;
     x.rt = y.rt = nullptr;
+    x.rt6 = y.rt6 = nullptr;
     return memcmp(&x, &y, sizeof(DevCfg)) == 0 && a.prog_key == b.prog_key &&
            (a.dcfg.crc_tab != nullptr) == (b.dcfg.crc_tab != nullptr) && a.cm == b.cm && a.ck == b.ck &&
            (a.fn != nullptr) == (b.fn != nullptr) && out_part(&a.job.out) == out_part(&b.job.out) &&
@@ -320,7 +321,8 @@ static int agg_submit(fcgpu_ctx *c, uint32_t slot, const fcgpu_job &j, uint32_t 
     it.fn = nullptr;
     it.prog_key = c->cfg.classify == FCGPU_CLS_PROGRAM ? c->prog_key
                 : c->cfg.classify == FCGPU_CLS_LB_TABLE ? c->lbtab_key
-                : c->cfg.classify == FCGPU_CLS_ROUTE ? c->rt_key : 0;
+                : c->cfg.classify == FCGPU_CLS_ROUTE ? c->rt_key
+                : c->cfg.classify == FCGPU_CLS_ROUTE6 ? (c->rt6_key ^ (c->rt_key << 1 | c->rt_key >> 63)) | 1 : 0;
     if (c->cfg.classify == FCGPU_CLS_PROGRAM && !c->jit_src.empty()) {
         const bool ip4 = it.cm == FCGPU_CHECK_IP4 || it.cm == FCGPU_MARK_IP4;
         it.fn = jit_function(c, jit_key((int)it.cm, it.ck, out_part(&j.out), ip4 && c->cfg.l4_mode != FCGPU_L4_NONE,

@@ -12,7 +12,7 @@
 //     checked_output_push_batch kills batches sent to a missing output
 //     (include/click/batchelement.hh:54-62).
 // Annotation offsets follow include/click/packet_anno.hh: DST_IP @0 (4),
-// IP6_NXT @16 (1), VLAN_TCI @20 (2), AGGREGATE @20 (4), BATCH_COUNT @24 (2).
+// DST_IP6 @0 (16, over DST_IP), IP6_NXT @16 (1), VLAN_TCI @20 (2), AGGREGATE @20 (4), BATCH_COUNT @24 (2).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -26,7 +26,7 @@
 
 namespace fcx {
 
-enum { ANNO_SIZE = 48, DST_IP_ANNO_OFFSET = 0, IP6_NXT_ANNO_OFFSET = 16, PAINT_ANNO_OFFSET = 17,
+enum { ANNO_SIZE = 48, DST_IP_ANNO_OFFSET = 0, DST_IP6_ANNO_OFFSET = 0, IP6_NXT_ANNO_OFFSET = 16, PAINT_ANNO_OFFSET = 17,
        VLAN_TCI_ANNO_OFFSET = 20, AGGREGATE_ANNO_OFFSET = 20, BATCH_COUNT_ANNO_OFFSET = 24 };
 
 class PacketPool;

@@ -35,6 +35,7 @@ class Sink : public Element {
                 if (_r->out_batch) _r->out_batch[i] = bi;
                 if (_r->out_agg) _r->out_agg[i] = p->anno_u32(AGGREGATE_ANNO_OFFSET);
                 if (_r->out_dst) _r->out_dst[i] = p->anno_u32(DST_IP_ANNO_OFFSET);
+                if (_r->out_dst6) memcpy(_r->out_dst6 + 16 * (size_t)i, p->anno_u8() + DST_IP6_ANNO_OFFSET, 16);
                 if (_r->out_len) _r->out_len[i] = p->length();
                 if (_r->out_nh) _r->out_nh[i] = p->network_header_offset();
                 if (_r->out_paint) _r->out_paint[i] = p->anno_u8(PAINT_ANNO_OFFSET);
@@ -176,7 +177,8 @@ static int run_graph(const char *conf, const uint8_t *arena, const uint32_t *des
 
 static const char *const kHandlerNames[] = {"count",      "drops",           "drop_details", "port_counts",
                                             "flow_count", "flow_count_fids", "flow_drops",   "gpu_errors",
-                                            "gpu_retries", "error",           "table"};
+                                            "gpu_retries", "error",           "table",
+                                            "table6"};
 static std::string read_all(Element *el) {
     std::string h;
     for (const char *name : kHandlerNames) h += std::string(name) + "=" + el->read_handler(name) + "\n";

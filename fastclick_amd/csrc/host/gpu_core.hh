@@ -60,6 +60,15 @@
 //     packet with no route is killed. N defaults to the largest OUT + 1. Static:
 //     the `table` handler prints the routes, there are no write handlers. MODE
 //     CHECK or MARK; not with LB_MODE, HASHSWITCH or PROGRAM.
+//   ROUTES6 "ADDR/PLEN [GW] OUT, ..."          -- LookupIP6Route behind GetIP6Address(24)
+//     (lookupip6route.cc:98-149): each IPv6 packet leaves on its longest matching
+//     prefix's OUT with GW, or else its own ip6_dst, in the 16-byte DST_IP6
+//     annotation; a later route for one ADDR/PLEN replaces the earlier one; a
+//     packet with no route is killed. MODE AUTO or MARK6. With ROUTES under MODE
+//     AUTO a dual stack: IPv4 packets take ROUTES (none given: no route). N
+//     defaults to the largest OUT + 1 over both lists. The `table6` handler
+//     prints the table as IP6Table::dump does. Not with LB_MODE, HASHSWITCH or
+//     PROGRAM.
 //   L4 UDP|TCP, L4_CHECKSUM (default true)   -- CheckUDPHeader / CheckTCPHeader
 //     behind the IPv4 check (MODE CHECK or MARK); their drops join output N
 //   COLOR (PAINT annotation on every packet)  -- IPInputCombo (with OFFSET 14,
@@ -156,6 +165,9 @@ class RxCore {
         bool n_set = false, other_cls = false;     // N given; LB_MODE / HASHSWITCH / PROGRAM given
         _routes.clear();
         _routes_set = false;
+        _routes6.clear();
+        _gw6.clear();
+        _routes6_set = false;
         std::vector<uint32_t> if_bad, if_good;   // INTERFACES (raw network-order words)
         for (const auto &raw : conf) {
             ConfArg a = parse_arg(raw);
@@ -219,6 +231,10 @@ class RxCore {
                 std::string e = parse_routes(v);
                 if (!e.empty()) return err(errh, "ROUTES: " + e);
                 _routes_set = true;
+            } else if (k == "ROUTES6") {
+                std::string e = parse_routes6(v);
+                if (!e.empty()) return err(errh, "ROUTES6: " + e);
+                _routes6_set = true;
             } else if (k == "LB_MODE") {
                 // LoadBalancer modetrans (include/click/loadbalancer.hh:23-58)
                 other_cls = true;
@@ -381,7 +397,24 @@ class RxCore {
             for (size_t j = 0; j < if_good.size(); ++j) _cfg.gooddst[j] = if_good[j];
         }
         if (!strip_set) _strip = (_cfg.check_mode == FCGPU_CHECK_AUTO);
-        if (_routes_set) {
+        if (_routes6_set) {
+            if (other_cls) return err(errh, "ROUTES6 conflicts with LB_MODE, HASHSWITCH and PROGRAM");
+            if (_cfg.check_mode != FCGPU_CHECK_AUTO && _cfg.check_mode != FCGPU_MARK_IP6)
+                return err(errh, "ROUTES6 needs MODE AUTO or MARK6");
+            if (_routes_set && _cfg.check_mode != FCGPU_CHECK_AUTO)
+                return err(errh, "ROUTES with ROUTES6 (a dual stack) needs MODE AUTO");
+            uint32_t top = 0;
+            for (const fcgpu_route6 &r : _routes6) top = r.port > top ? r.port : top;
+            for (const fcgpu_route &r : _routes) top = r.port > top ? r.port : top;
+            if (!n_set) _cfg.nports = top + 1;
+            _cfg.classify = FCGPU_CLS_ROUTE6;
+            static const uint8_t any[16] = {0};
+            if (fcgpu_route6_lookup(_routes6.data(), (uint32_t)_routes6.size(), _cfg.nports, any, nullptr) < -1)
+                return err(errh, std::string("ROUTES6: ") + fcgpu_last_error(nullptr));
+            if (_routes_set &&
+                fcgpu_route_lookup(_routes.data(), (uint32_t)_routes.size(), _cfg.nports, 0, nullptr) < -1)
+                return err(errh, std::string("ROUTES: ") + fcgpu_last_error(nullptr));
+        } else if (_routes_set) {
             // IPRouteTable::configure (iproutetable.cc:102-124): outputs below
             // noutputs; the table itself is checked as fcgpu_set_routes will
             if (other_cls) return err(errh, "ROUTES conflicts with LB_MODE, HASHSWITCH and PROGRAM");
@@ -454,6 +487,47 @@ class RxCore {
         return std::string();
     }
 
+    // ROUTES6: LookupIP6Route's arguments in one string, "ADDR/PLEN [GW] OUT"
+    // separated by commas (lookupip6route.cc:52-86; GW may be "-" or "::").
+    // The gateways are numbered as fcgpu_set_routes6 numbers them: by first
+    // appearance in the list. Returns "" or what is wrong.
+    std::string parse_routes6(std::string text) {
+        if (text.size() >= 2 && text.front() == '"' && text.back() == '"') text = text.substr(1, text.size() - 2);
+        static const uint8_t zero[16] = {0};
+        for (const std::string &arg : split_conf(text)) {
+            std::istringstream ss(arg);
+            std::vector<std::string> w;
+            for (std::string x; ss >> x;) w.push_back(x);
+            const std::string bad = "'" + arg + "' should be 'ADDR/PLEN [GATEWAY] OUTPUT'";
+            fcgpu_route6 r{};
+            long plen = 128, port;
+            if (w.size() < 2 || w.size() > 3) return bad;
+            const size_t slash = w[0].rfind('/');
+            if (slash != std::string::npos && (!parse_int(w[0].substr(slash + 1), plen) || plen < 0 || plen > 128))
+                return "'" + w[0] + "': the prefix length is not 0..128";
+            if (inet_pton(AF_INET6, w[0].substr(0, slash).c_str(), r.addr) != 1) return bad;
+            if (w.size() == 3 && w[1] != "-" && inet_pton(AF_INET6, w[1].c_str(), r.gw) != 1) return bad;
+            if (!parse_int(w.back(), port)) return bad;
+            if (port < 0 || port >= FCGPU_MAX_PORTS) return "'" + arg + "' bad OUTPUT";
+            for (int j = 0; j < 16; ++j) {                   // addr &= mask
+                const long bits = plen - 8 * j;
+                r.addr[j] = bits >= 8 ? r.addr[j] : bits <= 0 ? 0 : (uint8_t)(r.addr[j] & (0xff00u >> bits));
+            }
+            r.plen = (uint8_t)plen;
+            r.port = (uint8_t)port;
+            if (memcmp(r.gw, zero, 16)) {
+                bool seen = false;
+                for (const Addr6 &g : _gw6) seen |= memcmp(g.b, r.gw, 16) == 0;
+                if (!seen) {
+                    _gw6.push_back(Addr6{});
+                    memcpy(_gw6.back().b, r.gw, 16);
+                }
+            }
+            _routes6.push_back(r);
+        }
+        return std::string();
+    }
+
     int64_t timer_us() const { return _timer_us; }
     int error_output() const { return _error_output; }
     const fcgpu_cfg &device_cfg() const { return _cfg; }
@@ -488,9 +562,13 @@ class RxCore {
             if (rc == FCGPU_OK) rc = fcgpu_set_lb_table(_ctx, ring.data(), (uint32_t)ring.size());
             if (rc != FCGPU_OK) return err(errh, std::string("fcgpu_set_lb_table: ") + fcgpu_last_error(_ctx));
         }
-        if (_cfg.classify == FCGPU_CLS_ROUTE) {
+        if (_cfg.classify == FCGPU_CLS_ROUTE || (_cfg.classify == FCGPU_CLS_ROUTE6 && _routes_set)) {
             rc = fcgpu_set_routes(_ctx, _routes.data(), (uint32_t)_routes.size());
             if (rc != FCGPU_OK) return err(errh, std::string("fcgpu_set_routes: ") + fcgpu_last_error(_ctx));
+        }
+        if (_cfg.classify == FCGPU_CLS_ROUTE6) {
+            rc = fcgpu_set_routes6(_ctx, _routes6.data(), (uint32_t)_routes6.size());
+            if (rc != FCGPU_OK) return err(errh, std::string("fcgpu_set_routes6: ") + fcgpu_last_error(_ctx));
         }
         if (_flow_cap) {
             fcgpu_flow_config fc{_flow_mgr, _flow_cap, _flow_timeout, _flow_recycle_ms};
@@ -722,8 +800,32 @@ class RxCore {
         }
         return s;
     }
+    // The `table6` handler: the table as IP6Table::dump prints it
+    // (lib/ip6table.cc:86-98): a replaced route keeps its slot and shows the
+    // last values given. Configuration only.
+    std::string routes6_text() const {
+        std::string s = _routes6.empty() ? "" : "# Active routes\n";
+        auto same = [](const fcgpu_route6 &a, const fcgpu_route6 &b) {
+            return a.plen == b.plen && memcmp(a.addr, b.addr, 16) == 0;
+        };
+        for (size_t i = 0; i < _routes6.size(); ++i) {
+            size_t last = i;
+            bool earlier = false;
+            for (size_t j = 0; j < i; ++j) earlier |= same(_routes6[j], _routes6[i]);
+            if (earlier) continue;
+            for (size_t j = i + 1; j < _routes6.size(); ++j)
+                if (same(_routes6[j], _routes6[i])) last = j;
+            const fcgpu_route6 &r = _routes6[last];
+            char a[INET6_ADDRSTRLEN], g[INET6_ADDRSTRLEN];
+            inet_ntop(AF_INET6, r.addr, a, sizeof a);
+            inet_ntop(AF_INET6, r.gw, g, sizeof g);
+            s += std::string(a) + "/" + std::to_string(r.plen) + "\t" + g + "\t" + std::to_string(r.port) + "\n";
+        }
+        return s;
+    }
     std::string read_handler(const std::string &h) {
         if (h == "table") return routes_text();
+        if (h == "table6") return routes6_text();
         uint64_t c[FCGPU_NCOUNTERS];
         HostStats hs;
         std::string error;
@@ -1069,6 +1171,9 @@ class RxCore {
         constexpr uint32_t kAhead = 16;
         const bool hashing = _cfg.hash_mode != FCGPU_HASH_NONE;
         const bool autom = _cfg.check_mode == FCGPU_CHECK_AUTO;
+        const bool route6 = _cfg.classify == FCGPU_CLS_ROUTE6;
+        const Addr6 *const gw6 = _gw6.data();
+        const uint32_t ngw6 = (uint32_t)_gw6.size();
         // loop invariants in locals: the annotation stores below may alias
         // any member of a matching type, so the compiler reloads members
         const int color = _color;
@@ -1110,6 +1215,12 @@ class RxCore {
                 if (a.length < P::length(p)) P::take(p, P::length(p) - a.length);
                 if (a.ipver == 6) P::set_anno_u8(p, P::kIp6Nxt, a.ip6_nxt);
                 else P::set_anno_u32(p, P::kDstIp, a.dst_ip);
+                if (route6 && a.ipver == 6 && reason == FCGPU_R_OK) {
+                    // GetIP6Address(24), then LookupIP6Route's gateway if the route has one:
+                    // a.dst_ip is its id (fastclick_gpu.h, fcgpu_set_routes6)
+                    const uint32_t id = a.dst_ip;
+                    P::set_dst_ip6_anno(p, id && id <= ngw6 ? gw6[id - 1].b : P::data(p) + a.nh + 24u);
+                }
                 if (hashing && reason <= FCGPU_R_NO_MATCH)                       // AggregateHash (not after an L4 drop)
                     P::set_anno_u32(p, P::kAggregate, hash[i]);
                 if (flowid && flowid[i] != FCGPU_FLOW_NONE && flowid[i] != FCGPU_FLOW_FULL)
@@ -1191,7 +1302,8 @@ class RxCore {
     template <class Idx, class Emit>
     void emit_run(Slot &s, uint32_t port, uint32_t b, uint32_t e, Idx idx, Emit &emit) {
         const bool nomatch = port == _cfg.nports &&
-                             (_cfg.classify == FCGPU_CLS_PROGRAM || _cfg.classify == FCGPU_CLS_ROUTE);
+                             (_cfg.classify == FCGPU_CLS_PROGRAM || _cfg.classify == FCGPU_CLS_ROUTE ||
+                              _cfg.classify == FCGPU_CLS_ROUTE6);
         const bool last = port == _cfg.nports;
         if (nomatch || (last && _cfg.rewrite) || s.flowid || s.holes) {
             // the last list mixes invalid packets (output N) and packets no
@@ -1255,6 +1367,10 @@ class RxCore {
     uint32_t _cst_buckets = 0;        // CST_BUCKETS (0: 100 per output)
     std::vector<fcgpu_route> _routes; // ROUTES, addr &= mask applied
     bool _routes_set = false;
+    struct Addr6 { uint8_t b[16]; };
+    std::vector<fcgpu_route6> _routes6; // ROUTES6, addr &= mask applied
+    std::vector<Addr6> _gw6;          // its distinct gateways: id - 1 -> address
+    bool _routes6_set = false;
     ParsedProgram _prog;
     uint32_t _prog_kind = FCGPU_PROG_IPFILTER;
     bool _prog_jit = true;

@@ -30,6 +30,7 @@ struct ModelPolicy {
     static void set_anno_u8(Packet *p, int o, uint8_t v) { p->set_anno_u8(o, v); }
     static void set_anno_u16(Packet *p, int o, uint16_t v) { p->set_anno_u16(o, v); }
     static void set_anno_u32(Packet *p, int o, uint32_t v) { p->set_anno_u32(o, v); }
+    static void set_dst_ip6_anno(Packet *p, const uint8_t *a) { memcpy(p->anno_u8() + DST_IP6_ANNO_OFFSET, a, 16); }
     static void set_headers(Packet *p, uint32_t nh, uint32_t th) { p->set_network_header((int)nh, (int)th); }
     static void take(Packet *p, uint32_t n) { p->take(n); }
     static void pull(Packet *p, uint32_t n) { p->pull(n); }

@@ -96,15 +96,15 @@ def run_device(ctx: N.Context, dbatch: DeviceBatch, outs: DeviceOutputs, stream=
 
 
 def process_batch(batch, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
-                  program=None, program_jit=False, lb_table=None, routes=None):
+                  program=None, program_jit=False, lb_table=None, routes=None, routes6=None):
     """One batch on a fresh context (see process_batches)."""
     return process_batches([batch], cfg, anno=anno, perm=perm, device_index=device_index,
                            partition=partition, program=program, program_jit=program_jit,
-                           lb_table=lb_table, routes=routes)[0]
+                           lb_table=lb_table, routes=routes, routes6=routes6)[0]
 
 
 def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
-                    program=None, max_flows=0, program_jit=False, lb_table=None, routes=None):
+                    program=None, max_flows=0, program_jit=False, lb_table=None, routes=None, routes6=None):
     """Upload host Batches, run the device path over them in order on one
     context, return per-batch numpy results and the running counter vector.
     Convenience for tests and smoke(). program: optional (kind, steps,
@@ -112,7 +112,9 @@ def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, parti
     with program_jit (fcgpu_program_jit); max_flows > 0 enables the flow table
     (its state carries across the batches); lb_table: the CLS_LB_TABLE table
     (fcgpu_set_lb_table); routes: the CLS_ROUTE route table (fcgpu_set_routes,
-    the forms of _native.routes_array)."""
+    the forms of _native.routes_array); routes6: the CLS_ROUTE6 IPv6 table
+    (fcgpu_set_routes6, the forms of _native.routes6_array), next to which
+    routes is the IPv4 half of a dual stack."""
     torch = _torch()
     res = []
     with torch.cuda.device(device_index):
@@ -126,6 +128,8 @@ def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, parti
                 ctx.set_lb_table(lb_table)
             if routes is not None:
                 ctx.set_routes(routes)
+            if routes6 is not None:
+                ctx.set_routes6(routes6)
             if max_flows:
                 ctx.flow_enable(max_flows)
             for batch in batches:

@@ -12,7 +12,7 @@
 CLICK_DECLS
 
 enum { h_count, h_drops, h_drop_details, h_port_counts, h_flow_count, h_flow_count_fids, h_flow_drops,
-       h_gpu_errors, h_gpu_retries, h_error, h_table };
+       h_gpu_errors, h_gpu_retries, h_error, h_table, h_table6 };
 
 GPUIPCheckClassify::GPUIPCheckClassify() : _timer_us(100), _error_output(-1)
 {
@@ -166,14 +166,14 @@ String
 GPUIPCheckClassify::read_handler(Element *e, void *thunk)
 {
     GPUIPCheckClassify *g = static_cast<GPUIPCheckClassify *>(e);
-    if ((int)(uintptr_t)thunk == h_table) {
+    if ((int)(uintptr_t)thunk == h_table || (int)(uintptr_t)thunk == h_table6) {
         // the ROUTES table is configuration: a throw-away core re-reads it
         // (no device), as configure() does
         Core probe;
         std::string err;
         if (probe.configure(g->_conf, err) < 0)
             return String();
-        return String(probe.read_handler("table").c_str());
+        return String(probe.read_handler((int)(uintptr_t)thunk == h_table ? "table" : "table6").c_str());
     }
     static const char *const names[] = {"count", "drops", "drop_details", "port_counts", "flow_count",
                                         "flow_count_fids", "flow_drops", "gpu_errors", "gpu_retries", "error"};
@@ -221,6 +221,7 @@ GPUIPCheckClassify::add_handlers()
     add_read_handler("gpu_retries", read_handler, h_gpu_retries);
     add_read_handler("error", read_handler, h_error);
     add_read_handler("table", read_handler, h_table);
+    add_read_handler("table6", read_handler, h_table6);
 }
 
 CLICK_ENDDECLS

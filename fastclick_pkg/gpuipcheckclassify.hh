@@ -35,6 +35,8 @@
 #include <click/timestamp.hh>
 #include <click/sync.hh>
 #include "gpu_core.hh"   // -I fastclick_amd/csrc/host (Makefile)
+// after gpu_core.hh: clicknet/ip6.h defines ip6_nxt as a macro, fcgpu_anno has a field of that name
+#include <click/ip6address.hh>
 CLICK_DECLS
 
 struct ClickPolicy {
@@ -52,6 +54,9 @@ struct ClickPolicy {
     static void set_anno_u8(Packet *p, int o, uint8_t v) { p->set_anno_u8(o, v); }
     static void set_anno_u16(Packet *p, int o, uint16_t v) { p->set_anno_u16(o, v); }
     static void set_anno_u32(Packet *p, int o, uint32_t v) { p->set_anno_u32(o, v); }
+    static void set_dst_ip6_anno(Packet *p, const uint8_t *a) {
+        SET_DST_IP6_ANNO(p, IP6Address(reinterpret_cast<const unsigned char *>(a)));
+    }
     // set_ip_header / set_ip6_header (packet.hh:2493-2516): network header
     // at nh, transport header at th
     static void set_headers(Packet *p, uint32_t nh, uint32_t th) {

@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 26
+#define FCGPU_ABI_VERSION 27
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -124,6 +124,19 @@ extern "C" {
                                    FCGPU_R_NO_MATCH. The annotation is the header's ip_dst
                                    word, as after GetIPAddress(16) (MARK_IP4, which sets
                                    none itself, gets it too). IPv4 check modes only */
+#define FCGPU_CLS_ROUTE6     8  /* LookupIP6Route behind GetIP6Address(24) (elements/ip6/
+                                   lookupip6route.cc:98-149): longest-prefix lookup of the
+                                   header's ip6_dst in the table set by fcgpu_set_routes6;
+                                   the route's output, its gateway *id* into anno.dst_ip
+                                   (0: no gateway, and for a packet without a route); no
+                                   route -> FCGPU_R_NO_MATCH. CHECK_AUTO and MARK_IP6 only.
+                                   MARK_IP6 checks no length, as GetIP6Address does not: a
+                                   frame shorter than nh + 40 is looked up on whatever bytes
+                                   follow it (inside the arena's slack), whatever hash_mode.
+                                   Under CHECK_AUTO an IPv4 packet is looked up as
+                                   FCGPU_CLS_ROUTE does in the table of fcgpu_set_routes
+                                   (none set: no route); anno.ipver tells which meaning
+                                   dst_ip has */
 
 /* l4_mode: a CheckUDPHeader / CheckTCPHeader after the IPv4 check (CHECK_IP4 or
  * MARK_IP4 only). The checksum covers the whole L4 segment, so with
@@ -559,6 +572,41 @@ int  fcgpu_set_routes(fcgpu_ctx *ctx, const fcgpu_route *routes, uint32_t n);
  * -2 for a route list fcgpu_set_routes would refuse (-1 is "no route";
  * fcgpu_last_error(NULL) has the message). Host-only (no device, no context). */
 int  fcgpu_route_lookup(const fcgpu_route *routes, uint32_t n, uint32_t nports, uint32_t addr, uint32_t *gw);
+
+/* The route table of FCGPU_CLS_ROUTE6 (LookupIP6Route's "ADDR/PLEN [GW] OUT"
+ * routes): addr and gw are the 16 address bytes in network order (gw all zero
+ * = no gateway), plen the prefix length 0..128 (addr &= mask is applied; only
+ * contiguous masks exist here), port the output. A second route for one
+ * addr/plen replaces the first, as IP6Table::add does (lib/ip6table.cc:52-73).
+ * fcgpu_anno has no room for a 16-byte gateway, so a routed IPv6 packet's
+ * anno.dst_ip is a gateway id: 0 for a route without gateway, else 1 + the
+ * position of the route's gateway among the distinct non-zero gateways in
+ * order of first appearance in `routes` -- the caller can number them itself.
+ * fcgpu_set_routes6 replaces the context's table (n 0: an empty table); plen >
+ * 128, a port >= the configured nports (checked here and at every submission,
+ * for the IPv4 table of a dual-stack context too), more than 32767 distinct
+ * (gateway id, port) next hops, or a device image above 256 MiB is
+ * FCGPU_EINVAL and keeps the previous table, as an allocation failure does. On
+ * the device the table is a path-compressed 16-8-...-8 trie of 32-bit entries
+ * (DESIGN.md 3.7): 256 KiB + 1040 B per surviving chunk + 8 B per next hop.
+ * Synchronises the device before replacing a table. */
+typedef struct fcgpu_route6 {
+    uint8_t  addr[16], gw[16];
+    uint8_t  plen;            /* 0..128                                                   */
+    uint8_t  port;            /* output                                                   */
+    uint16_t reserved;
+} fcgpu_route6;
+int  fcgpu_set_routes6(fcgpu_ctx *ctx, const fcgpu_route6 *routes, uint32_t n);
+/* The same trie walked as the device walks it: the output port of addr's
+ * longest matching prefix, or -1 (no route); *gw_id (may be NULL) = its gateway
+ * id. nports 0: outputs unbounded. -2 for a route list fcgpu_set_routes6 would
+ * refuse (fcgpu_last_error(NULL) has the message). Host-only. */
+int  fcgpu_route6_lookup(const fcgpu_route6 *routes, uint32_t n, uint32_t nports, const uint8_t addr[16],
+                         uint32_t *gw_id);
+/* The trie's shape: the chunks that survive path compression, and the longest
+ * walk in dependent loads (the root load + one per chunk; the next hop is not
+ * counted). FCGPU_EINVAL for a refused list. Host-only. */
+int  fcgpu_route6_stats(const fcgpu_route6 *routes, uint32_t n, uint32_t *chunks, uint32_t *max_loads);
 
 /* Flow table: the IPFlow5ID flow classification of
  * FlowIPManagerHMP (elements/research/flowipmanagerhmp.cc:96-126; the

@@ -71,6 +71,7 @@ typedef struct fcclick_result {
                                the source stopped (may be NULL)                          */
     uint32_t *out_batch;    /* [n] index of the PacketBatch the packet arrived in at its
                                sink, in arrival order over all sinks (may be NULL)    */
+    uint8_t  *out_dst6;     /* [n][16] DST_IP6_ANNO (anno bytes 0..15) on departure (may be NULL) */
 } fcclick_result;
 
 /* burst value for a non-batch upstream: the source calls the element's

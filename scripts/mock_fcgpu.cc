@@ -165,6 +165,16 @@ int fcgpu_route_lookup(const fcgpu_route *, uint32_t, uint32_t, uint32_t, uint32
     if (gw) *gw = 0;
     return -1;
 }
+int fcgpu_set_routes6(fcgpu_ctx *, const fcgpu_route6 *, uint32_t) { return FCGPU_OK; }
+int fcgpu_route6_lookup(const fcgpu_route6 *, uint32_t, uint32_t, const uint8_t *, uint32_t *gw_id) {
+    if (gw_id) *gw_id = 0;
+    return -1;
+}
+int fcgpu_route6_stats(const fcgpu_route6 *, uint32_t, uint32_t *chunks, uint32_t *max_loads) {
+    if (chunks) *chunks = 0;
+    if (max_loads) *max_loads = 1;
+    return FCGPU_OK;
+}
 int fcgpu_lb_hash_ring(uint32_t nsel, uint32_t size, uint8_t *out) {
     for (uint32_t i = 0; i < size; ++i) out[i] = (uint8_t)(nsel ? i % nsel : 0);
     return FCGPU_OK;
