@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 27
+ABI_VERSION = 28
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -36,6 +36,8 @@ CHECK_IP4, MARK_IP4, CHECK_AUTO, MARK_IP6 = 0, 1, 2, 3
 HASH_NONE, HASH_FLOWID, HASH_FLOW5ID = 0, 1, 2
 CLS_NONE, CLS_LB_HASH, CLS_HASH_IP, CLS_HASHSWITCH, CLS_PROGRAM, CLS_LB_CRC, CLS_LB_TABLE, CLS_ROUTE = range(8)
 CLS_ROUTE6 = 8
+CLS_STRING = 9
+AC_LDS_TABLE = 36 * 1024   # fcgpu_match.hh kAcLdsTable: class map + transitions staged in LDS up to this
 PROG_IPFILTER, PROG_CLASSIFIER = 0, 1
 STEP_SHORT_YES = 1
 MAX_STEPS = 8192
@@ -210,6 +212,10 @@ FCGPU_SYMBOLS = {
     "fcgpu_set_routes6": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "fcgpu_route6_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint32)]),
     "fcgpu_route6_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fcgpu_set_patterns": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_patterns_match": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32,
+                                       C.POINTER(C.c_uint32)]),
+    "fcgpu_patterns_stats": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4),
     "fcgpu_set_host_threads": (C.c_int, [C.c_void_p, C.c_uint32]),
     "fcgpu_span_submit": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                     C.POINTER(fcgpu_out)]),
@@ -411,6 +417,43 @@ def route6_stats(routes):
     return chunks.value, loads.value
 
 
+def _patterns(patterns):
+    """(concatenated bytes, uint32 lengths array, n) of a sequence of byte strings."""
+    pats = [bytes(p) for p in patterns]
+    lens = (C.c_uint32 * max(len(pats), 1))(*[len(p) for p in pats])
+    return b"".join(pats), lens, len(pats)
+
+
+def patterns_match(patterns, text, nports: int = 0):
+    """fcgpu_patterns_match: (id, end) of AhoCorasick::match_first over `text`
+    -- the pattern whose match ends earliest, the longest of those ending
+    there; end = the bytes of text up to and including the match -- or (-1, 0).
+    The automaton is built and walked as on the device. Host-only. Raises
+    ValueError for a pattern list fcgpu_set_patterns refuses."""
+    blob, lens, n = _patterns(patterns)
+    text = bytes(text)
+    end = C.c_uint32(0)
+    lib = load()
+    pid = lib.fcgpu_patterns_match(blob, lens, n, nports, text, len(text), C.byref(end))
+    if pid < -1:
+        raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
+    return pid, end.value
+
+
+def patterns_stats(patterns):
+    """fcgpu_patterns_stats: dict(states, classes, image_bytes, lmax, in_lds)
+    of the automaton built from `patterns`; in_lds: its transitions are staged
+    in LDS by the pre-pass (else read from global memory)."""
+    blob, lens, n = _patterns(patterns)
+    v = [C.c_uint32(0) for _ in range(4)]
+    lib = load()
+    if lib.fcgpu_patterns_stats(blob, lens, n, *[C.byref(x) for x in v]) != OK:
+        raise ValueError((lib.fcgpu_last_error(None) or b"").decode())
+    states, classes, image, lmax = (x.value for x in v)
+    return dict(states=states, classes=classes, image_bytes=image, lmax=lmax,
+                in_lds=(256 + 2 * states * classes + 15) // 16 * 16 <= AC_LDS_TABLE)
+
+
 def default_cfg() -> fcgpu_cfg:
     cfg = fcgpu_cfg()
     lib = _lib
@@ -600,6 +643,12 @@ class Context:
         replaces the previous one."""
         r = routes6_array(routes)
         self._chk(self.lib.fcgpu_set_routes6(self.h, r.ctypes.data, len(r)), "fcgpu_set_routes6")
+
+    def set_patterns(self, patterns):
+        """The patterns of CLS_STRING (a sequence of byte strings, pattern k
+        -> output k); replaces the previous ones."""
+        blob, lens, n = _patterns(patterns)
+        self._chk(self.lib.fcgpu_set_patterns(self.h, blob, lens, n), "fcgpu_set_patterns")
 
     def set_lb_table(self, table):
         """The bucket -> output table of CLS_LB_TABLE (uint8 sequence)."""

@@ -167,6 +167,8 @@ void fcgpu_close(fcgpu_ctx *c) {
         hipFree(c->d_lbtab);
         hipFree(c->d_routes);
         hipFree(c->d_routes6);
+        hipFree(c->d_ac);
+        hipFree(c->d_acrec);
         hipFree(c->d_verdict);
         hipFree(c->d_arena);
         hipFree(c->d_desc);
@@ -261,7 +263,9 @@ int fcgpu_configure(fcgpu_ctx *c, const fcgpu_cfg *cfg) {
     const bool ip4mode = cfg->check_mode == FCGPU_CHECK_IP4 || cfg->check_mode == FCGPU_MARK_IP4;
     if (cfg->vlan_ethertype > 0xffff) return fail(c, FCGPU_EINVAL, "bad vlan_ethertype");
     if (cfg->hash_mode > FCGPU_HASH_FLOW5ID) return fail(c, FCGPU_EINVAL, "bad hash_mode");
-    if (cfg->classify > FCGPU_CLS_ROUTE6) return fail(c, FCGPU_EINVAL, "bad classify mode");
+    if (cfg->classify > FCGPU_CLS_STRING) return fail(c, FCGPU_EINVAL, "bad classify mode");
+    if (cfg->classify == FCGPU_CLS_STRING && !ip4mode)
+        return fail(c, FCGPU_EINVAL, "FCGPU_CLS_STRING: IPv4 check modes only (CHECK_IP4 or MARK_IP4)");
     if (cfg->classify == FCGPU_CLS_ROUTE6 && cfg->check_mode != FCGPU_CHECK_AUTO && cfg->check_mode != FCGPU_MARK_IP6)
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE6 looks up the header's ip6_dst: CHECK_AUTO and MARK_IP6 only");
     if (cfg->classify == FCGPU_CLS_ROUTE && !ip4mode)
@@ -339,6 +343,8 @@ int fcgpu_configure(fcgpu_ctx *c, const fcgpu_cfg *cfg) {
     d.rt6 = c->dev_rt6();
     d.rt6_hop_off = c->rt6_hop_off;
     d.rt6_nhops = c->rt6_nhops;
+    d.ac_rec = c->dev_acrec();
+    d.ac_npat = c->ac_npat;
     d.prog = c->d_prog;
     d.prog_n = c->prog_n;
     d.prog_q = c->prog_q;

@@ -63,6 +63,8 @@ struct DevCfg {
     const uint32_t *rt6;      // FCGPU_CLS_ROUTE6: root[65536], then 1040-B chunks (host/route6_table.hh)
     uint32_t rt6_hop_off;     // byte offset of its next hops ({gw id, port}, 8 B each) from rt6
     uint32_t rt6_nhops;       // next hops, entry 0 (no route) included
+    const uint32_t *ac_rec;   // FCGPU_CLS_STRING: k_acmatch's record per packet of the batch (fcgpu_match.hh)
+    uint32_t ac_npat;         // its patterns: the output of a packet without a match
 };
 
 // Device step: x = (u16)offset | flags << 16, y = value, z = mask,
@@ -302,6 +304,23 @@ __device__ __forceinline__ uint32_t route_apply(const DevCfg &c, uint2 hop, fcgp
     }
     if (hop.x) an.dst_ip = hop.x;
     return hop.y;
+}
+
+// ---- FCGPU_CLS_STRING: StringClassifier over k_acmatch's records -----------
+// rec: the packet's record (fcgpu_match.hh): end << 16 | (1 + id) of the
+// earliest match in the whole frame, 0 = none. It counts iff it ends inside
+// the packet as the checks left it (CheckIPHeader's trim to ip_len); a later
+// one proves that nothing ends inside. No match: output npatterns, and where
+// that does not exist the packet is killed as a program's unmatched one is
+// (checked_output_push, stringclassifier.cc:94-101).
+__device__ __forceinline__ uint32_t match_apply(const DevCfg &c, uint32_t rec, uint32_t length, uint32_t &reason) {
+    const bool hit = rec && (rec >> 16) <= length;
+    const uint32_t port = hit ? (rec & 0xffffu) - 1u : c.ac_npat;
+    if (port >= c.nports) {
+        reason = FCGPU_R_NO_MATCH;
+        return c.nports;
+    }
+    return port;
 }
 
 // ---- FCGPU_CLS_ROUTE6: LookupIP6Route over the path-compressed trie ---------
@@ -708,6 +727,10 @@ __device__ __forceinline__ void process_packet(const DevCfg &c, const FrameView 
         r.port = route_apply(c, hop, an, r.reason);
         return;
     }
+    if (ROUTE == 3) {   // FCGPU_CLS_STRING: rx_tile's match_apply sets the port
+        r.port = 0;
+        return;
+    }
     if (ROUTE == 1) {   // FCGPU_CLS_ROUTE (IPv4 check modes): the general path probes once the checks are done
         an.dst_ip = h[4];   // the chain's GetIPAddress(16): MarkIPHeader alone leaves the annotation unset
         r.port = route_apply(c, route_walk(c, sprog, h[4], route_probe(c, h[4])), an, r.reason);
@@ -764,7 +787,7 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
     for (int j = 0; j < 6; ++j) h[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
     // FCGPU_CLS_ROUTE: the trie's first entry, loaded while the checks run
     uint32_t rt0 = 0;
-    if (ROUTE) rt0 = route_probe(c, h[4]);
+    if (ROUTE == 1) rt0 = route_probe(c, h[4]);
     // CheckIPHeader::valid reason chain, computed as predicates (no divergent
     // branches); the first failing check wins, as in the reference
     const uint32_t plen = len - o;
@@ -803,7 +826,7 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
     }
     uint32_t port = 0;
     if (ROUTE) {
-        // below, with the annotation the gateway goes into
+        // below, with the annotation the gateway goes into (1); rx_tile's match_apply (3)
     } else if (c.classify == FCGPU_CLS_LB_HASH) {
         port = (uint32_t)lb_port(hv, c.nports, c.lb_magic);
     } else if (c.classify == FCGPU_CLS_LB_CRC) {       // wave-uniform
@@ -836,7 +859,7 @@ __device__ __forceinline__ bool ip4_fast(const DevCfg &c, const FrameView &f, ui
         port = run_program(c, f, an, sprog);
         if (port >= c.nports) r.reason = FCGPU_R_NO_MATCH;
     }
-    if (ROUTE && ok) port = route_apply(c, route_walk(c, sprog, h[4], rt0), an, r.reason);
+    if (ROUTE == 1 && ok) port = route_apply(c, route_walk(c, sprog, h[4], rt0), an, r.reason);
     r.port = ok && port < c.nports ? port : c.nports;
     return true;
 }
@@ -1512,6 +1535,8 @@ __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const 
     PktResult r;
     r.an = fcgpu_anno{};
     uint32_t bin = 0xffffffffu, rslot = 0xffffffffu;
+    uint32_t rec = 0;   // FCGPU_CLS_STRING: the pre-pass's record, loaded while the checks run
+    if (ROUTE == 3 && live) rec = A.cfg.ac_rec[i];
     if (FAST && CM == FCGPU_CHECK_IP4) {
         bool done = !live;
         if (live) done = ip4_fast<CK, PROG, ROUTE>(A.cfg, f, d.y, (uint32_t)A.cfg.offset, r, sprog);
@@ -1533,6 +1558,7 @@ __device__ __forceinline__ void rx_tile(const RxArgs &A, const RxView &V, const 
     } else if (live) {
         process_packet<CM, CK, PROG, ROUTE>(A.cfg, f, d.y, r, sprog);
     }
+    if (ROUTE == 3 && live && r.reason == FCGPU_R_OK) r.port = match_apply(A.cfg, rec, r.an.length, r.reason);
     if (L4) l4_stage(A.cfg, f, V.arena + d.x, live, r);
     FlowProbe fq;
     if (FLOW) fq = flow_issue(FL, f, live, r);
@@ -1656,7 +1682,8 @@ struct RxLaunch {
 };
 
 // ROUTE: 1 = the FCGPU_CLS_ROUTE classifier (IPv4 check modes), 2 =
-// FCGPU_CLS_ROUTE6 (CHECK_AUTO, MARK_IP6), each compiled only into the kernels
+// FCGPU_CLS_ROUTE6 (CHECK_AUTO, MARK_IP6), 3 = FCGPU_CLS_STRING (IPv4 check
+// modes, one batch per launch), each compiled only into the kernels
 // launched for it, as PROG is for decision programs: the other instances keep
 // their classify chain as it was.
 template <int CM, bool CK, int PART, bool PROG, bool L4, bool FLOW = false,

@@ -3,7 +3,8 @@
 // its slot and queue records, and the host helpers one unit defines and
 // others call (namespace fcgpu_rt). Host code only; the kernels each unit
 // launches come from the device header it alone includes:
-//   fcgpu_launch.hip        k_rx instantiations (fcgpu_device.hh)
+//   fcgpu_launch.hip        k_rx instantiations (fcgpu_device.hh), the
+//                           payload pre-pass (fcgpu_match.hh)
 //   fcgpu_process.hip       whole-batch partition scan/scatter, mbuf
 //                           descriptors (fcgpu_part.hh)
 //   fcgpu_flow_api.hip      new-flow passes, maintainer (fcgpu_flow.hh)
@@ -236,6 +237,13 @@ struct fcgpu_ctx {
     const uint32_t *dev_rt6() const {
         return cfg.classify == FCGPU_CLS_ROUTE6 ? reinterpret_cast<const uint32_t *>(d_routes6) : nullptr;
     }
+    uint8_t *d_ac = nullptr;                  // CLS_STRING automaton image (fcgpu_set_patterns, host/ac_table.hh)
+    uint32_t *d_acrec = nullptr;              // [max_batch] k_acmatch's records, made with the first table
+    uint32_t ac_out_off = 0, ac_nclasses = 0, ac_first_final = 0, ac_lmax = 0;
+    uint32_t ac_npat = 0;                     // patterns: ids 0 .. ac_npat - 1, no match -> output ac_npat
+    uint64_t ac_key = 0;                      // hash of the image (0: none)
+    uint32_t ncu = 0;                         // the device's compute units (k_acmatch's grid)
+    const uint32_t *dev_acrec() const { return cfg.classify == FCGPU_CLS_STRING && d_ac ? d_acrec : nullptr; }
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)
@@ -357,6 +365,9 @@ hipError_t launch_rx_any(int part, uint32_t cm, bool ck, const RxLaunch &L, uint
 hipError_t launch_rx_one(int part, uint32_t cm, bool ck, const RxArgs &a, hipStream_t s, hipEvent_t e0,
                          hipEvent_t e1, fcgpu_ctx *jc);
 hipError_t launch_rx_fn(hipFunction_t fn, int part, const RxLaunch &L, uint32_t grid, hipStream_t s);
+// FCGPU_CLS_STRING's pre-pass (k_acmatch) over one batch, into c->d_acrec
+hipError_t launch_acmatch(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, uint32_t n, uint32_t layout,
+                          hipStream_t s);
 
 // ---- fcgpu_process.hip ------------------------------------------------------
 int check_process(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, uint32_t n, const fcgpu_out *o);

@@ -3,8 +3,10 @@
 // (launch_rx_any), compiled programs through their hiprtc module
 // (jit_function), and the host-side launch guard every launch passes
 // (rx_launch_ok, fcgpu_launch_guard_selftest). The only unit that
-// instantiates k_rx.
+// instantiates k_rx; k_acmatch (fcgpu_match.hh), the pre-pass of
+// FCGPU_CLS_STRING, is launched here too.
 #include "fcgpu_internal.hh"
+#include "fcgpu_match.hh"
 
 using namespace fcgpu;
 using namespace fcgpu_rt;
@@ -81,6 +83,50 @@ static hipError_t launch_rx_route6(uint32_t cm, bool ck, const RxLaunch &L, uint
     return hipSuccess;
 }
 
+// FCGPU_CLS_STRING: the IPv4 check modes, one batch per launch (the records are
+// indexed by the packet's place in its batch); refused without the records.
+template <int PART>
+static hipError_t launch_rx_match(uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0,
+                                  hipEvent_t e1) {
+    if (!L.A.cfg.ac_rec || L.njobs != 1) return hipErrorInvalidValue;
+    if (cm == FCGPU_MARK_IP4) launch_rx_ip4<FCGPU_MARK_IP4, false, PART, false, 3>(L, grid, s, e0, e1, nullptr);
+    else if (cm != FCGPU_CHECK_IP4) return hipErrorInvalidValue;
+    else if (ck) launch_rx_ip4<FCGPU_CHECK_IP4, true, PART, false, 3>(L, grid, s, e0, e1, nullptr);
+    else launch_rx_ip4<FCGPU_CHECK_IP4, false, PART, false, 3>(L, grid, s, e0, e1, nullptr);
+    return hipSuccess;
+}
+
+// The pre-pass over one batch. The table goes to LDS when the class map and
+// next[] fit kAcLdsTable, else only the class map does; the grid is what the
+// device holds at once (workgroups per CU by their LDS, at most 8), each
+// workgroup looping over 16-packet steps.
+hipError_t launch_acmatch(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, uint32_t n, uint32_t layout,
+                          hipStream_t s) {
+    if (!c->d_ac || !c->d_acrec || !arena || !desc || n > c->max_batch || (layout & ~kLayKnown))
+        return hipErrorInvalidValue;
+    AcArgs a;
+    a.arena = arena;
+    a.desc = reinterpret_cast<const uint2 *>(desc);
+    a.n = n;
+    a.layout = layout;
+    a.rec = c->d_acrec;
+    a.image = c->d_ac;
+    a.out_off = c->ac_out_off;
+    a.nclasses = c->ac_nclasses;
+    a.first_final = c->ac_first_final;
+    a.lmax = c->ac_lmax;
+    a.chunk = ac_chunk(c->ac_lmax);
+    const bool tab = ac_next_in_lds(c->ac_out_off);
+    a.table_q = tab ? c->ac_out_off / 16u : 16u;
+    const size_t lds = ac_lds_bytes(a);
+    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
+    const uint32_t steps = (n + kAcGroups - 1) / kAcGroups;
+    const uint32_t grid = std::min(steps, std::max(1u, c->ncu) * per_cu);
+    if (tab) hipLaunchKernelGGL(k_acmatch<true>, dim3(grid), dim3(kTile), lds, s, a);
+    else hipLaunchKernelGGL(k_acmatch<false>, dim3(grid), dim3(kTile), lds, s, a);
+    return hipGetLastError();
+}
+
 template <int PART, bool PROG>
 static void launch_rx_part(uint32_t cm, bool ck, const RxLaunch &L, uint32_t grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1, fcgpu_ctx *jc) {
     switch (cm * 2 + (ck ? 1 : 0)) {
@@ -141,6 +187,10 @@ hipError_t launch_rx_any(int part, uint32_t cm, bool ck, const RxLaunch &L, uint
         return part == kPartTile     ? launch_rx_route6<kPartTile>(cm, ck, L, grid, s, e0, e1)
                : part == kPartGlobal ? launch_rx_route6<kPartGlobal>(cm, ck, L, grid, s, e0, e1)
                                      : launch_rx_route6<kPartNone>(cm, ck, L, grid, s, e0, e1);
+    if (L.A.cfg.classify == FCGPU_CLS_STRING)
+        return part == kPartTile     ? launch_rx_match<kPartTile>(cm, ck, L, grid, s, e0, e1)
+               : part == kPartGlobal ? launch_rx_match<kPartGlobal>(cm, ck, L, grid, s, e0, e1)
+                                     : launch_rx_match<kPartNone>(cm, ck, L, grid, s, e0, e1);
     if (L.A.cfg.classify == FCGPU_CLS_PROGRAM) launch_rx_prog<true>(part, cm, ck, L, grid, s, e0, e1, jc);
     else launch_rx_prog<false>(part, cm, ck, L, grid, s, e0, e1, jc);
     return hipSuccess;

@@ -31,6 +31,8 @@ int check_process(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, 
     if (c->cfg.classify == FCGPU_CLS_ROUTE6 &&
         (!c->d_routes6 || c->rt6_max_port >= c->cfg.nports || (c->d_routes && c->rt_max_port >= c->cfg.nports)))
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE6 without fcgpu_set_routes6, or a route table with outputs >= nports");
+    if (c->cfg.classify == FCGPU_CLS_STRING && (!c->d_ac || !c->d_acrec || c->ac_npat > c->cfg.nports))
+        return fail(c, FCGPU_EINVAL, "FCGPU_CLS_STRING without fcgpu_set_patterns of at most nports patterns");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n && (!d_arena || !d_desc)) return fail(c, FCGPU_EINVAL, "null arena/desc");
     if (o->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");
@@ -104,6 +106,8 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
         HIPCHK(c, hipEventRecord(c->flow_order[0], c->stream));
         HIPCHK(c, hipStreamWaitEvent(s, c->flow_order[0], 0));
     }
+    // FCGPU_CLS_STRING: the payload pre-pass leaves the batch's records for k_rx
+    if (c->cfg.classify == FCGPU_CLS_STRING) HIPCHK(c, launch_acmatch(c, d_arena, d_desc, n, layout, s));
     HIPCHK(c, launch_rx_one(part, c->cfg.check_mode, c->cfg.checksum != 0, a, s, timed ? ev[0].a : nullptr,
                             timed ? ev[0].b : nullptr, c->jit_src.empty() ? nullptr : c));
     HIPCHK(c, hipGetLastError());
@@ -168,7 +172,8 @@ static bool fusable(const fcgpu_ctx *c, const fcgpu_job &j) {
     const bool global_ok = out_part(&j.out) != kPartGlobal || (!c->fl.slots && j.out.verdict);
     // header rewrites into the arena do not fuse (jobs may share an arena);
     // rewrites reported through ip_rw do
-    return j.n && !(c->cfg.rewrite & FCGPU_RW_INPLACE) && global_ok;
+    // FCGPU_CLS_STRING: the pre-pass's records are one array per context
+    return j.n && !(c->cfg.rewrite & FCGPU_RW_INPLACE) && global_ok && c->cfg.classify != FCGPU_CLS_STRING;
 }
 
 static bool outputs_overlap(const fcgpu_out &x, const fcgpu_out &y) {
@@ -649,6 +654,8 @@ int fcgpu_process_counted(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *
                           const uint32_t *d_count, uint32_t base, const fcgpu_out *o, void *stream) {
     if (!c || !o) return FCGPU_EINVAL;
     if (!d_count) return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: null count");
+    if (c->cfg.classify == FCGPU_CLS_STRING)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: FCGPU_CLS_STRING's pre-pass takes the host's packet count");
     // the whole-batch partition's scan and scatter take the host's n
     if (o->partition == FCGPU_PART_GLOBAL && (o->perm || o->port_start))
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: no whole-batch partition (FCGPU_PART_GLOBAL)");
@@ -666,11 +673,12 @@ int fcgpu_process_jobs(fcgpu_ctx *c, const fcgpu_job *jobs, uint32_t njobs, void
         const fcgpu_job &j = jobs[k];
         int rc = check_process(c, j.arena, j.desc, j.n, &j.out);
         if (rc != FCGPU_OK) return rc;
-        const bool shared = c->fl.slots || (j.out.partition == FCGPU_PART_GLOBAL && (j.out.perm || j.out.port_start));
+        const bool shared = c->fl.slots || c->cfg.classify == FCGPU_CLS_STRING ||
+                            (j.out.partition == FCGPU_PART_GLOBAL && (j.out.perm || j.out.port_start));
         if ((j.stream ? j.stream : stream) != (jobs[0].stream ? jobs[0].stream : stream)) split = true;
         if (split && shared)
-            return fail(c, FCGPU_EINVAL, "jobs on several streams: the flow table and the whole-batch "
-                                         "partition use context scratch (one stream only)");
+            return fail(c, FCGPU_EINVAL, "jobs on several streams: the flow table, the whole-batch partition and "
+                                         "FCGPU_CLS_STRING use context scratch (one stream only)");
     }
     HIPCHK(c, hipSetDevice(c->device));
     auto eff = [&](const fcgpu_job &j) { return (hipStream_t)(j.stream ? j.stream : stream); };
@@ -714,6 +722,8 @@ int fcgpu_process_jobs(fcgpu_ctx *c, const fcgpu_job *jobs, uint32_t njobs, void
 int fcgpu_process_host(fcgpu_ctx *c, const uint8_t *const *frames, const uint32_t *lens, uint32_t n,
                        const fcgpu_out *h) {
     if (!c || !h || (n && (!frames || !lens))) return FCGPU_EINVAL;
+    if (c->cfg.classify == FCGPU_CLS_STRING)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_host: FCGPU_CLS_STRING scans whole frames, this path stages headers");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n == 0) return FCGPU_OK;
     if (h->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");
@@ -776,6 +786,8 @@ int fcgpu_pool_register(fcgpu_ctx *c, void *base, size_t bytes) {
 int fcgpu_process_mbufs(fcgpu_ctx *c, void *const *mbufs, uint32_t n, const fcgpu_mbuf_layout *L,
                         const fcgpu_out *o, void *stream) {
     if (!c || !o || !L || (n && !mbufs)) return FCGPU_EINVAL;
+    if (c->cfg.classify == FCGPU_CLS_STRING)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: FCGPU_CLS_STRING is served by fcgpu_process and fcgpu_process_jobs");
     if (!c->pool_host) return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: no pool registered (fcgpu_pool_register)");
     if (L->header_bytes > 64 || L->buf_addr + 8 > L->header_bytes || L->data_off + 2 > L->header_bytes ||
         L->data_len + 2 > L->header_bytes || (L->buf_addr & 7) || (L->data_off & 1) || (L->data_len & 1))

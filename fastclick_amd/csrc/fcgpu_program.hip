@@ -2,10 +2,12 @@
 // IPClassifier / Classifier): upload with jump tables
 // (build_tables), compiled programs (fcgpu_program_jit, hiprtc through
 // prog_jit.hh), the LoadBalancer hash tables (FCGPU_CLS_LB_TABLE) and the
-// route tables (FCGPU_CLS_ROUTE, FCGPU_CLS_ROUTE6).
+// route tables (FCGPU_CLS_ROUTE, FCGPU_CLS_ROUTE6) and the pattern automaton
+// (FCGPU_CLS_STRING).
 #include "fcgpu_internal.hh"
 #include "host/route_table.hh"
 #include "host/route6_table.hh"
+#include "host/ac_table.hh"
 #include "jit_sources.inc"   // kJitDeviceHh, kJitAbiH (fastclick_amd/build.py)
 
 using namespace fcgpu;
@@ -379,6 +381,78 @@ int fcgpu_route6_stats(const fcgpu_route6 *routes, uint32_t n, uint32_t *chunks,
         return fail(nullptr, FCGPU_EINVAL, "fcgpu_route6_stats: " + (why.empty() ? std::string("null routes") : why));
     if (chunks) *chunks = t.nchunks();
     if (max_loads) *max_loads = t.max_loads;
+    return FCGPU_OK;
+}
+
+// FCGPU_CLS_STRING: the automaton of host/ac_table.hh, one image, and the
+// per-packet record scratch of its pre-pass (made with the first table, in one
+// group with it); same contract as fcgpu_set_routes.
+int fcgpu_set_patterns(fcgpu_ctx *c, const uint8_t *bytes, const uint32_t *lens, uint32_t n) {
+    if (!c) return FCGPU_EINVAL;
+    if (n && (!bytes || !lens)) return fail(c, FCGPU_EINVAL, "fcgpu_set_patterns: null patterns");
+    if (agg_queued(c)) return fail(c, FCGPU_EINVAL, "fcgpu_set_patterns: a queued span submission is not waited for");
+    fcac::Image im;
+    std::string why;
+    if (fcac::build(bytes, lens, n, c->configured ? c->cfg.nports : 0, im, why) != FCGPU_OK)
+        return fail(c, FCGPU_EINVAL, "fcgpu_set_patterns: " + why);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    if (!c->ncu) {
+        int cu = 0;
+        HIPCHK(c, hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->ncu = (uint32_t)std::max(cu, 1);
+    }
+    // uploaded before the old table is freed: a failure leaves it intact
+    uint8_t *nt = nullptr;
+    uint32_t *rec = nullptr;
+    const size_t rec_bytes = sizeof(uint32_t) * std::max(c->max_batch, 1u);
+    if (int rc = c->d_acrec ? alloc_or_fail(c, "fcgpu_set_patterns", {dev_buf(nt, im.bytes.size())})
+                            : alloc_or_fail(c, "fcgpu_set_patterns",
+                                            {dev_buf(nt, im.bytes.size()), dev_buf(rec, rec_bytes, true)}))
+        return rc;
+    if (hipError_t e = hipMemcpy(nt, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice)) {
+        (void)hipFree(nt);
+        (void)hipFree(rec);
+        return fail(c, FCGPU_ERUNTIME, std::string("fcgpu_set_patterns upload: ") + hipGetErrorString(e));
+    }
+    hipFree(c->d_ac);
+    c->d_ac = nt;
+    if (rec) c->d_acrec = rec;
+    c->ac_out_off = im.out_off;
+    c->ac_nclasses = im.nclasses;
+    c->ac_first_final = im.first_final;
+    c->ac_lmax = im.lmax;
+    c->ac_npat = n;
+    uint64_t key = 1469598103934665603ull;
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(im.bytes.data());      // the image is a multiple of 16 B
+    for (size_t k = 0; k < im.bytes.size() / 8; ++k) key = (key ^ w[k]) * 1099511628211ull;
+    c->ac_key = (key ^ im.bytes.size()) | 1;
+    c->dcfg.ac_rec = c->dev_acrec();
+    c->dcfg.ac_npat = n;
+    return FCGPU_OK;
+}
+
+int fcgpu_patterns_match(const uint8_t *bytes, const uint32_t *lens, uint32_t n, uint32_t nports, const uint8_t *text,
+                         uint32_t len, uint32_t *end) {
+    fcac::Image im;
+    std::string why;
+    if ((n && (!bytes || !lens)) || (len && !text) || fcac::build(bytes, lens, n, nports, im, why) != FCGPU_OK) {
+        fail(nullptr, FCGPU_EINVAL, "fcgpu_patterns_match: " + (why.empty() ? std::string("null argument") : why));
+        return -2;
+    }
+    return fcac::match_first(im, text, len, end);
+}
+
+int fcgpu_patterns_stats(const uint8_t *bytes, const uint32_t *lens, uint32_t n, uint32_t *states, uint32_t *classes,
+                         uint32_t *image_bytes, uint32_t *lmax) {
+    fcac::Image im;
+    std::string why;
+    if ((n && (!bytes || !lens)) || fcac::build(bytes, lens, n, 0, im, why) != FCGPU_OK)
+        return fail(nullptr, FCGPU_EINVAL, "fcgpu_patterns_stats: " + (why.empty() ? std::string("null patterns") : why));
+    if (states) *states = im.nstates;
+    if (classes) *classes = im.nclasses;
+    if (image_bytes) *image_bytes = (uint32_t)im.bytes.size();
+    if (lmax) *lmax = im.lmax;
     return FCGPU_OK;
 }
 

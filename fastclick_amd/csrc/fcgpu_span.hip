@@ -118,6 +118,7 @@ static bool agg_compatible(const AggItem &a, const AggItem &b) {
     x.lb_tab = y.lb_tab = nullptr;
     x.rt = y.rt = nullptr;
     x.rt6 = y.rt6 = nullptr;
+    x.ac_rec = y.ac_rec = nullptr;
     return memcmp(&x, &y, sizeof(DevCfg)) == 0 && a.prog_key == b.prog_key &&
            (a.dcfg.crc_tab != nullptr) == (b.dcfg.crc_tab != nullptr) && a.cm == b.cm && a.ck == b.ck &&
            (a.fn != nullptr) == (b.fn != nullptr) && out_part(&a.job.out) == out_part(&b.job.out) &&
@@ -322,7 +323,8 @@ static int agg_submit(fcgpu_ctx *c, uint32_t slot, const fcgpu_job &j, uint32_t 
     it.prog_key = c->cfg.classify == FCGPU_CLS_PROGRAM ? c->prog_key
                 : c->cfg.classify == FCGPU_CLS_LB_TABLE ? c->lbtab_key
                 : c->cfg.classify == FCGPU_CLS_ROUTE ? c->rt_key
-                : c->cfg.classify == FCGPU_CLS_ROUTE6 ? (c->rt6_key ^ (c->rt_key << 1 | c->rt_key >> 63)) | 1 : 0;
+                : c->cfg.classify == FCGPU_CLS_ROUTE6 ? (c->rt6_key ^ (c->rt_key << 1 | c->rt_key >> 63)) | 1
+                : c->cfg.classify == FCGPU_CLS_STRING ? c->ac_key : 0;
     if (c->cfg.classify == FCGPU_CLS_PROGRAM && !c->jit_src.empty()) {
         const bool ip4 = it.cm == FCGPU_CHECK_IP4 || it.cm == FCGPU_MARK_IP4;
         it.fn = jit_function(c, jit_key((int)it.cm, it.ck, out_part(&j.out), ip4 && c->cfg.l4_mode != FCGPU_L4_NONE,
@@ -403,6 +405,8 @@ extern "C" {
 int fcgpu_span_submit(fcgpu_ctx *c, uint32_t slot, const uint8_t *h_span, size_t bytes, const uint32_t *h_desc,
                       uint32_t n, const fcgpu_out *h) {
     if (!c || !h || slot >= FCGPU_SPAN_SLOTS || (n && (!h_span || !h_desc))) return FCGPU_EINVAL;
+    if (c->cfg.classify == FCGPU_CLS_STRING)
+        return fail(c, FCGPU_EINVAL, "fcgpu_span_submit: FCGPU_CLS_STRING is served by fcgpu_process and fcgpu_process_jobs");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (bytes > 0xffffffffull - kArenaPad) return fail(c, FCGPU_EINVAL, "span larger than 4 GiB");
     SpanSlot &sp = c->span[slot];
@@ -677,6 +681,9 @@ int fcgpu_span_reserve(fcgpu_ctx *c, size_t in_bytes, uint32_t outputs, uint32_t
 int fcgpu_span_submit_block(fcgpu_ctx *c, uint32_t slot, const void *h_in, size_t in_bytes, size_t desc_off,
                             size_t frames_off, uint32_t n, void *h_out, uint32_t outputs, uint32_t partition) {
     if (!c || slot >= FCGPU_SPAN_SLOTS || (n && (!h_in || !h_out))) return FCGPU_EINVAL;
+    if (c->cfg.classify == FCGPU_CLS_STRING)
+        return fail(c, FCGPU_EINVAL,
+                    "fcgpu_span_submit_block: FCGPU_CLS_STRING is served by fcgpu_process and fcgpu_process_jobs");
     const bool force_copy = (outputs & FCGPU_SUBMIT_COPY) != 0;
     const bool desc32 = (outputs & FCGPU_SUBMIT_DESC32) != 0;
     outputs &= ~(FCGPU_SUBMIT_COPY | FCGPU_SUBMIT_DESC32);

@@ -96,15 +96,16 @@ def run_device(ctx: N.Context, dbatch: DeviceBatch, outs: DeviceOutputs, stream=
 
 
 def process_batch(batch, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
-                  program=None, program_jit=False, lb_table=None, routes=None, routes6=None):
+                  program=None, program_jit=False, lb_table=None, routes=None, routes6=None, patterns=None):
     """One batch on a fresh context (see process_batches)."""
     return process_batches([batch], cfg, anno=anno, perm=perm, device_index=device_index,
                            partition=partition, program=program, program_jit=program_jit,
-                           lb_table=lb_table, routes=routes, routes6=routes6)[0]
+                           lb_table=lb_table, routes=routes, routes6=routes6, patterns=patterns)[0]
 
 
 def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
-                    program=None, max_flows=0, program_jit=False, lb_table=None, routes=None, routes6=None):
+                    program=None, max_flows=0, program_jit=False, lb_table=None, routes=None, routes6=None,
+                    patterns=None):
     """Upload host Batches, run the device path over them in order on one
     context, return per-batch numpy results and the running counter vector.
     Convenience for tests and smoke(). program: optional (kind, steps,
@@ -114,7 +115,8 @@ def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, parti
     (fcgpu_set_lb_table); routes: the CLS_ROUTE route table (fcgpu_set_routes,
     the forms of _native.routes_array); routes6: the CLS_ROUTE6 IPv6 table
     (fcgpu_set_routes6, the forms of _native.routes6_array), next to which
-    routes is the IPv4 half of a dual stack."""
+    routes is the IPv4 half of a dual stack; patterns: the CLS_STRING byte
+    strings (fcgpu_set_patterns)."""
     torch = _torch()
     res = []
     with torch.cuda.device(device_index):
@@ -130,6 +132,8 @@ def process_batches(batches, cfg, *, anno=True, perm=True, device_index=0, parti
                 ctx.set_routes(routes)
             if routes6 is not None:
                 ctx.set_routes6(routes6)
+            if patterns is not None:
+                ctx.set_patterns(patterns)
             if max_flows:
                 ctx.flow_enable(max_flows)
             for batch in batches:

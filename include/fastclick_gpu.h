@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 27
+#define FCGPU_ABI_VERSION 28
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -137,6 +137,21 @@ extern "C" {
                                    FCGPU_CLS_ROUTE does in the table of fcgpu_set_routes
                                    (none set: no route); anno.ipver tells which meaning
                                    dst_ip has */
+#define FCGPU_CLS_STRING     9  /* StringClassifier (elements/ids/stringclassifier.cc:94-101)
+                                   over the patterns set by fcgpu_set_patterns: the packet
+                                   goes to the output of AhoCorasick::match_first's pattern
+                                   (ahocorasickplus.hh:113-123, ahocorasick.c:177-243,
+                                   node.c:425-442) -- the one whose match ends earliest, of
+                                   several ending there the longest; output = its index in
+                                   the list. No match -> output npatterns, and where that
+                                   output does not exist (npatterns == nports)
+                                   FCGPU_R_NO_MATCH, as checked_output_push kills it. The
+                                   text is the frame from its descriptor offset (byte 0,
+                                   link header included) up to anno.length, i.e. after
+                                   CheckIPHeader's trim to ip_len (MARK_IP4: the whole
+                                   frame): a pattern found only in padding past ip_len is no
+                                   match. IPv4 check modes only; served by fcgpu_process and
+                                   fcgpu_process_jobs */
 
 /* l4_mode: a CheckUDPHeader / CheckTCPHeader after the IPv4 check (CHECK_IP4 or
  * MARK_IP4 only). The checksum covers the whole L4 segment, so with
@@ -607,6 +622,39 @@ int  fcgpu_route6_lookup(const fcgpu_route6 *routes, uint32_t n, uint32_t nports
  * walk in dependent loads (the root load + one per chunk; the next hop is not
  * counted). FCGPU_EINVAL for a refused list. Host-only. */
 int  fcgpu_route6_stats(const fcgpu_route6 *routes, uint32_t n, uint32_t *chunks, uint32_t *max_loads);
+
+/* The patterns of FCGPU_CLS_STRING: n byte strings concatenated in `bytes`,
+ * lens[k] the length of pattern k (1..1024, AC_PATTRN_MAX_LENGTH,
+ * actypes.h:165); pattern k's output is k. fcgpu_set_patterns replaces the
+ * context's automaton (n 0: nothing matches). An empty or over-long pattern,
+ * a duplicate (the reference drops a duplicate with a warning and then counts
+ * its no-match output one too high; here it is refused), more patterns than
+ * the configured nports (checked here and at every submission), more than
+ * 65535 automaton states or a device image above 32 MiB is FCGPU_EINVAL and
+ * keeps the previous automaton, as an allocation failure does (the automaton
+ * and the per-packet scratch of the payload pre-pass, max_batch words made
+ * with the first table, are allocated as one group). On the device the
+ * automaton is a byte-class map and a dense uint16 DFA, which
+ * a pre-pass kernel runs over every frame before k_rx. Refused while a span
+ * submission is queued; synchronises the device before replacing a table.
+ * A CLS_STRING context's jobs (fcgpu_process_jobs) share one stream and are
+ * not fused; fcgpu_process_host, fcgpu_process_counted, fcgpu_process_mbufs,
+ * fcgpu_span_submit and fcgpu_span_submit_block return FCGPU_EINVAL. */
+int  fcgpu_set_patterns(fcgpu_ctx *ctx, const uint8_t *bytes, const uint32_t *lens, uint32_t n);
+/* The same automaton walked on the host: the id of match_first's pattern in
+ * text[0, len), or -1 (no match); *end (may be NULL) = the match's end
+ * position (1..len; 0 without a match). nports 0: ids unbounded. -2 for a list
+ * fcgpu_set_patterns would refuse (fcgpu_last_error(NULL) has the message).
+ * Host-only. */
+int  fcgpu_patterns_match(const uint8_t *bytes, const uint32_t *lens, uint32_t n, uint32_t nports, const uint8_t *text,
+                          uint32_t len, uint32_t *end);
+/* The automaton's shape: states, byte classes ("other" included), the device
+ * image in bytes and the longest pattern. The class map and transitions go to
+ * LDS when image_bytes minus the output table (2 B per final state) is at
+ * most 36 KiB, else the transitions are read from global memory.
+ * FCGPU_EINVAL for a refused list. Host-only. */
+int  fcgpu_patterns_stats(const uint8_t *bytes, const uint32_t *lens, uint32_t n, uint32_t *states, uint32_t *classes,
+                          uint32_t *image_bytes, uint32_t *lmax);
 
 /* Flow table: the IPFlow5ID flow classification of
  * FlowIPManagerHMP (elements/research/flowipmanagerhmp.cc:96-126; the

@@ -175,6 +175,19 @@ int fcgpu_route6_stats(const fcgpu_route6 *, uint32_t, uint32_t *chunks, uint32_
     if (max_loads) *max_loads = 1;
     return FCGPU_OK;
 }
+int fcgpu_set_patterns(fcgpu_ctx *, const uint8_t *, const uint32_t *, uint32_t) { return FCGPU_OK; }
+int fcgpu_patterns_match(const uint8_t *, const uint32_t *, uint32_t, uint32_t, const uint8_t *, uint32_t, uint32_t *end) {
+    if (end) *end = 0;
+    return -1;
+}
+int fcgpu_patterns_stats(const uint8_t *, const uint32_t *, uint32_t, uint32_t *states, uint32_t *classes,
+                         uint32_t *image_bytes, uint32_t *lmax) {
+    if (states) *states = 1;
+    if (classes) *classes = 1;
+    if (image_bytes) *image_bytes = 272;
+    if (lmax) *lmax = 0;
+    return FCGPU_OK;
+}
 int fcgpu_lb_hash_ring(uint32_t nsel, uint32_t size, uint8_t *out) {
     for (uint32_t i = 0; i < size; ++i) out[i] = (uint8_t)(nsel ? i % nsel : 0);
     return FCGPU_OK;
