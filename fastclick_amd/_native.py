@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 28
+ABI_VERSION = 29
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -139,6 +139,22 @@ class fcgpu_flow_stat(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("manager", "capacity", "count", "free_ids", "pending", "epochs")]
 
 
+AGGCOUNT_MAX_CAPACITY = 1 << 24
+
+
+class fcgpu_aggcount_config(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("capacity", "bytes", "ip_bytes", "mask")]
+
+
+class fcgpu_aggcount_stat(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("capacity", "nagg", "nnz", "frozen")] + \
+               [(k, C.c_uint64) for k in ("count", "seen", "uncounted")]
+
+
+class fcgpu_aggcount_rec(C.Structure):
+    _fields_ = [("agg", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
+
+
 class fcgpu_out(C.Structure):
     _fields_ = [
         ("verdict", C.c_void_p),
@@ -238,6 +254,11 @@ FCGPU_SYMBOLS = {
     "fcgpu_flow_set_time": (C.c_int, [C.c_void_p, C.c_uint32]),
     "fcgpu_flow_maintain": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "fcgpu_flow_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_flow_stat)]),
+    "fcgpu_aggcount_configure": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_aggcount_config)]),
+    "fcgpu_aggcount_freeze": (C.c_int, [C.c_void_p, C.c_int]),
+    "fcgpu_aggcount_reset": (C.c_int, [C.c_void_p]),
+    "fcgpu_aggcount_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_aggcount_stat)]),
+    "fcgpu_aggcount_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "fcgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fcgpu_host_free": (None, [C.c_void_p]),
     "fcgpu_pool_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -691,6 +712,35 @@ class Context:
         v = C.c_uint32()
         self._chk(self.lib.fcgpu_flow_count(self.h, C.byref(v)), "fcgpu_flow_count")
         return v.value
+
+    def aggcount_configure(self, capacity, bytes=False, ip_bytes=False, mask=0xFFFFFFFF):
+        """AggregateCounter behind the classifier (fcgpu_aggcount_configure):
+        one count per distinct hash & mask of the packets that leave with R_OK,
+        at most `capacity` of them; packets, or with bytes their trimmed
+        length (ip_bytes: from the network header on). 0 disables it."""
+        ac = fcgpu_aggcount_config(capacity, int(bytes), int(ip_bytes), mask)
+        self._chk(self.lib.fcgpu_aggcount_configure(self.h, C.byref(ac)), "fcgpu_aggcount_configure")
+
+    def aggcount_freeze(self, frozen=True):
+        self._chk(self.lib.fcgpu_aggcount_freeze(self.h, int(frozen)), "fcgpu_aggcount_freeze")
+
+    def aggcount_reset(self):
+        self._chk(self.lib.fcgpu_aggcount_reset(self.h), "fcgpu_aggcount_reset")
+
+    def aggcount_stats(self) -> dict:
+        st = fcgpu_aggcount_stat()
+        self._chk(self.lib.fcgpu_aggcount_stats(self.h, C.byref(st)), "fcgpu_aggcount_stats")
+        return {k: getattr(st, k) for k, _ in fcgpu_aggcount_stat._fields_}
+
+    def aggcount_read(self):
+        """(aggregates uint32, counts uint64): the non-zero counts, sorted by
+        aggregate (AggregateCounter's write_file order)."""
+        import numpy as np
+        n = C.c_uint32()
+        self._chk(self.lib.fcgpu_aggcount_read(self.h, None, 0, C.byref(n)), "fcgpu_aggcount_read")
+        rec = np.zeros(n.value, dtype=[("agg", "<u4"), ("reserved", "<u4"), ("count", "<u8")])
+        self._chk(self.lib.fcgpu_aggcount_read(self.h, rec.ctypes.data, n.value, C.byref(n)), "fcgpu_aggcount_read")
+        return rec["agg"][:n.value].copy(), rec["count"][:n.value].copy()
 
     def set_host_threads(self, n: int):
         self._chk(self.lib.fcgpu_set_host_threads(self.h, n), "fcgpu_set_host_threads")

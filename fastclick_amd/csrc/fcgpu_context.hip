@@ -191,6 +191,7 @@ void fcgpu_close(fcgpu_ctx *c) {
             if (sp.done) hipEventDestroy(sp.done);
         }
         flow_free(c);
+        aggcount_free(c);
         hipFree(c->d_mptr);
         hipFree(c->d_mdesc);
         hipFree(c->x_bsum);

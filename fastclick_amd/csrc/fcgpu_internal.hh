@@ -9,6 +9,8 @@
 //                           descriptors (fcgpu_part.hh)
 //   fcgpu_flow_api.hip      new-flow passes, maintainer (fcgpu_flow.hh)
 //   fcgpu_exchange_api.hip  flow re-shard (fcgpu_exchange.hh)
+//   fcgpu_aggcount_api.hip  AggregateCounter: its control calls, the
+//                           post-pass and the dump (fcgpu_aggcount.hh)
 // and the units without kernels:
 //   fcgpu_context.hip       open / configure / close, counters, timing,
 //                           errors, fault injection, host memory
@@ -244,6 +246,18 @@ struct fcgpu_ctx {
     uint64_t ac_key = 0;                      // hash of the image (0: none)
     uint32_t ncu = 0;                         // the device's compute units (k_acmatch's grid)
     const uint32_t *dev_acrec() const { return cfg.classify == FCGPU_CLS_STRING && d_ac ? d_acrec : nullptr; }
+    // AggregateCounter (fcgpu_aggcount_configure, fcgpu_aggcount.hh); agc_tab
+    // == nullptr: disabled. The table, its state words and the per-batch
+    // scratch k_rx writes where the caller left verdict / hash / anno NULL
+    // are one allocation group.
+    fcgpu_aggcount_config agc_conf{};         // mask never 0
+    unsigned long long *agc_tab = nullptr;    // [2 * agc_slots] {tag, count}
+    unsigned long long *agc_state = nullptr;  // [kAgcStateWords] totals, nagg, nnz
+    uint32_t agc_slots = 0;                   // next_pow2(2 * capacity)
+    bool agc_frozen = false;
+    uint16_t *agc_verdict = nullptr;          // [max_batch]
+    uint32_t *agc_hash = nullptr;             // [max_batch]
+    fcgpu_anno *agc_anno = nullptr;           // [max_batch]
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)
@@ -391,5 +405,12 @@ hipError_t flow_pass(fcgpu_ctx *c, const FlowArgs &F, uint32_t n, hipStream_t s)
 // / k * words, its epoch epoch0 + k)
 hipError_t flow_pass_fused(fcgpu_ctx *c, const FlowArgs &F, uint32_t g, const uint32_t *n,
                            uint32_t *const *flowid, uint32_t stride, uint32_t words, uint32_t epoch0, hipStream_t s);
+
+// ---- fcgpu_aggcount_api.hip -------------------------------------------------
+void aggcount_free(fcgpu_ctx *c);
+// AggregateCounter's post-pass (k_aggcount) over one batch's verdicts, hashes
+// and (byte modes) annotations
+hipError_t launch_aggcount(const fcgpu_ctx *c, const uint16_t *verdict, const uint32_t *hash, const fcgpu_anno *anno,
+                           uint32_t n, hipStream_t s);
 
 }  // namespace fcgpu_rt

@@ -33,6 +33,9 @@ int check_process(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, 
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_ROUTE6 without fcgpu_set_routes6, or a route table with outputs >= nports");
     if (c->cfg.classify == FCGPU_CLS_STRING && (!c->d_ac || !c->d_acrec || c->ac_npat > c->cfg.nports))
         return fail(c, FCGPU_EINVAL, "FCGPU_CLS_STRING without fcgpu_set_patterns of at most nports patterns");
+    if (c->agc_tab && c->cfg.hash_mode == FCGPU_HASH_NONE)
+        return fail(c, FCGPU_EINVAL, "the aggregate counter (fcgpu_aggcount_configure) needs a hash_mode: FCGPU_HASH_NONE "
+                                     "leaves no AGGREGATE annotation");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n && (!d_arena || !d_desc)) return fail(c, FCGPU_EINVAL, "null arena/desc");
     if (o->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");
@@ -71,6 +74,12 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
     a.verdict = verdict;
     a.hash = o->hash;
     a.anno = o->anno;
+    if (c->agc_tab) {   // the aggregate counter reads them behind k_rx: context scratch where the caller wants none
+        if (layout) return fail(c, FCGPU_EINVAL, "the aggregate counter reads fcgpu_anno records (public layouts only)");
+        if (!a.verdict) a.verdict = c->agc_verdict;
+        if (!a.hash) a.hash = c->agc_hash;
+        if (!a.anno && c->agc_conf.bytes) a.anno = c->agc_anno;
+    }
     a.tilecnt = c->d_tilecnt;
     a.perm = o->perm;
     a.tile_count = o->tile_count;
@@ -111,6 +120,7 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
     HIPCHK(c, launch_rx_one(part, c->cfg.check_mode, c->cfg.checksum != 0, a, s, timed ? ev[0].a : nullptr,
                             timed ? ev[0].b : nullptr, c->jit_src.empty() ? nullptr : c));
     HIPCHK(c, hipGetLastError());
+    if (c->agc_tab) HIPCHK(c, launch_aggcount(c, a.verdict, a.hash, a.anno, n, s));
     if (a.fl.slots) {   // the batch's new flows get their IDs (fcgpu_flow.hh)
         HIPCHK(c, flow_pass(c, a.fl, n, s));
         if (cross) {
@@ -172,8 +182,10 @@ static bool fusable(const fcgpu_ctx *c, const fcgpu_job &j) {
     const bool global_ok = out_part(&j.out) != kPartGlobal || (!c->fl.slots && j.out.verdict);
     // header rewrites into the arena do not fuse (jobs may share an arena);
     // rewrites reported through ip_rw do
-    // FCGPU_CLS_STRING: the pre-pass's records are one array per context
-    return j.n && !(c->cfg.rewrite & FCGPU_RW_INPLACE) && global_ok && c->cfg.classify != FCGPU_CLS_STRING;
+    // FCGPU_CLS_STRING: the pre-pass's records are one array per context, as
+    // the aggregate counter's substitute outputs are
+    return j.n && !(c->cfg.rewrite & FCGPU_RW_INPLACE) && global_ok && c->cfg.classify != FCGPU_CLS_STRING &&
+           !c->agc_tab;
 }
 
 static bool outputs_overlap(const fcgpu_out &x, const fcgpu_out &y) {
@@ -656,6 +668,8 @@ int fcgpu_process_counted(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *
     if (!d_count) return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: null count");
     if (c->cfg.classify == FCGPU_CLS_STRING)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: FCGPU_CLS_STRING's pre-pass takes the host's packet count");
+    if (c->agc_tab)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: the aggregate counter's post-pass takes the host's packet count");
     // the whole-batch partition's scan and scatter take the host's n
     if (o->partition == FCGPU_PART_GLOBAL && (o->perm || o->port_start))
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: no whole-batch partition (FCGPU_PART_GLOBAL)");
@@ -673,12 +687,12 @@ int fcgpu_process_jobs(fcgpu_ctx *c, const fcgpu_job *jobs, uint32_t njobs, void
         const fcgpu_job &j = jobs[k];
         int rc = check_process(c, j.arena, j.desc, j.n, &j.out);
         if (rc != FCGPU_OK) return rc;
-        const bool shared = c->fl.slots || c->cfg.classify == FCGPU_CLS_STRING ||
+        const bool shared = c->fl.slots || c->cfg.classify == FCGPU_CLS_STRING || c->agc_tab ||
                             (j.out.partition == FCGPU_PART_GLOBAL && (j.out.perm || j.out.port_start));
         if ((j.stream ? j.stream : stream) != (jobs[0].stream ? jobs[0].stream : stream)) split = true;
         if (split && shared)
-            return fail(c, FCGPU_EINVAL, "jobs on several streams: the flow table, the whole-batch partition and "
-                                         "FCGPU_CLS_STRING use context scratch (one stream only)");
+            return fail(c, FCGPU_EINVAL, "jobs on several streams: the flow table, the whole-batch partition, "
+                                         "FCGPU_CLS_STRING and the aggregate counter use context scratch (one stream only)");
     }
     HIPCHK(c, hipSetDevice(c->device));
     auto eff = [&](const fcgpu_job &j) { return (hipStream_t)(j.stream ? j.stream : stream); };
@@ -724,6 +738,8 @@ int fcgpu_process_host(fcgpu_ctx *c, const uint8_t *const *frames, const uint32_
     if (!c || !h || (n && (!frames || !lens))) return FCGPU_EINVAL;
     if (c->cfg.classify == FCGPU_CLS_STRING)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_host: FCGPU_CLS_STRING scans whole frames, this path stages headers");
+    if (c->agc_tab)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_host: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n == 0) return FCGPU_OK;
     if (h->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");
@@ -788,6 +804,8 @@ int fcgpu_process_mbufs(fcgpu_ctx *c, void *const *mbufs, uint32_t n, const fcgp
     if (!c || !o || !L || (n && !mbufs)) return FCGPU_EINVAL;
     if (c->cfg.classify == FCGPU_CLS_STRING)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: FCGPU_CLS_STRING is served by fcgpu_process and fcgpu_process_jobs");
+    if (c->agc_tab)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (!c->pool_host) return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: no pool registered (fcgpu_pool_register)");
     if (L->header_bytes > 64 || L->buf_addr + 8 > L->header_bytes || L->data_off + 2 > L->header_bytes ||
         L->data_len + 2 > L->header_bytes || (L->buf_addr & 7) || (L->data_off & 1) || (L->data_len & 1))

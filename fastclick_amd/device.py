@@ -95,6 +95,32 @@ def run_device(ctx: N.Context, dbatch: DeviceBatch, outs: DeviceOutputs, stream=
                 stream=s.cuda_stream, **outs.ptrs())
 
 
+def aggcount_configure(ctx: N.Context, capacity, bytes=False, ip_bytes=False, mask=0xFFFFFFFF):
+    """AggregateCounter on the device behind ctx's classifier
+    (fcgpu_aggcount_configure): every later run_device / run_jobs batch is
+    counted by the k_aggcount post-pass. capacity 0 disables it."""
+    ctx.aggcount_configure(capacity, bytes=bytes, ip_bytes=ip_bytes, mask=mask)
+
+
+def aggcount_freeze(ctx: N.Context, frozen=True):
+    ctx.aggcount_freeze(frozen)
+
+
+def aggcount_reset(ctx: N.Context):
+    ctx.aggcount_reset()
+
+
+def aggcount_stats(ctx: N.Context) -> dict:
+    """capacity, nagg, nnz, frozen, count, seen, uncounted (synchronises)."""
+    return ctx.aggcount_stats()
+
+
+def aggcount_read(ctx: N.Context):
+    """Two numpy arrays, aggregates (uint32, ascending) and their non-zero
+    counts (uint64) (synchronises)."""
+    return ctx.aggcount_read()
+
+
 def process_batch(batch, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
                   program=None, program_jit=False, lb_table=None, routes=None, routes6=None, patterns=None):
     """One batch on a fresh context (see process_batches)."""

@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 28
+#define FCGPU_ABI_VERSION 29
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -743,6 +743,73 @@ typedef struct fcgpu_flow_stat {
 } fcgpu_flow_stat;
 /* Synchronises the context's device work. */
 int  fcgpu_flow_stats(fcgpu_ctx *ctx, fcgpu_flow_stat *st);
+
+/* AggregateCounter (elements/analysis/aggcounter.{hh,cc}) behind the
+ * classifier: one 64-bit packet or byte count per distinct value of the
+ * AGGREGATE annotation, kept on the device across the context's batches until
+ * fcgpu_aggcount_reset. Per packet it is AggregateCounterBase<T>::update
+ * (aggcounter.cc:282-322), the path push_batch takes:
+ *   - the counter sits where the classifier's outputs rejoin: it sees a packet
+ *     iff its verdict reason is FCGPU_R_OK;
+ *   - agg = hash & mask, hash = the value fcgpu_out.hash carries; 0 and
+ *     0xffffffff are ordinary aggregates. cfg.hash_mode FCGPU_HASH_NONE with
+ *     the counter enabled is FCGPU_EINVAL at submission;
+ *   - amount: bytes 0: 1; bytes 1: anno.length (after the checker's trim);
+ *     bytes 1 and ip_bytes: anno.length - anno.nh. The EXTRA_PACKETS and
+ *     EXTRA_LENGTH annotations do not exist here and count as 0;
+ *   - frozen (the "freeze" handler, set between batches): only aggregates that
+ *     already have a node are updated, a packet of an unseen one is not
+ *     counted;
+ *   - capacity: at most `capacity` distinct aggregates get a node. An
+ *     aggregate that arrives when the table is full is refused, and from then
+ *     on every packet of it is, never a part of them; with at most `capacity`
+ *     distinct aggregates nothing is refused. The limit is this library's: the
+ *     reference grows until memory runs out;
+ *   - the reference's 32-bit Node::count is the low word of a count; nnz is
+ *     _num_nonzero.
+ * Out of scope: the keywords AGGREGATE_FREEZE, AGGREGATE_STOP, AGGREGATE_CALL
+ * and COUNT_* (they depend on the packet order inside a batch), the second,
+ * always-frozen input, write_ip_file, counts_pdf and banners.
+ * The counter is a post-pass kernel behind k_rx on the batch's stream
+ * (DESIGN.md 3.9); where the caller leaves fcgpu_out.verdict, hash or anno
+ * NULL, k_rx writes context scratch instead (max_batch entries, allocated with
+ * the table as one group: an allocation failure leaves the previous state).
+ * Served by fcgpu_process and fcgpu_process_jobs, with every check and
+ * classify mode; an enabled context's jobs share one stream and are not fused,
+ * and its fcgpu_process calls must all be on one stream too (the scratch is one
+ * set per context and nothing orders two streams that use it);
+ * fcgpu_process_host, fcgpu_process_counted, fcgpu_process_mbufs,
+ * fcgpu_span_submit and fcgpu_span_submit_block return FCGPU_EINVAL.
+ * configure and reset are refused while a span submission is queued and
+ * synchronise the device. */
+#define FCGPU_AGGCOUNT_MAX_CAPACITY (1u << 24)
+typedef struct fcgpu_aggcount_config {
+    uint32_t capacity;      /* distinct aggregates; 0 disables and frees. At most
+                               FCGPU_AGGCOUNT_MAX_CAPACITY */
+    uint32_t bytes, ip_bytes;
+    uint32_t mask;          /* 0 is taken as 0xffffffff */
+} fcgpu_aggcount_config;
+/* Replaces the counter (its counts are forgotten, it is not frozen). */
+int  fcgpu_aggcount_configure(fcgpu_ctx *ctx, const fcgpu_aggcount_config *cfg);
+int  fcgpu_aggcount_freeze(fcgpu_ctx *ctx, int frozen);
+/* "clear": forget every aggregate and the totals; frozen stays. */
+int  fcgpu_aggcount_reset(fcgpu_ctx *ctx);
+typedef struct fcgpu_aggcount_stat {
+    uint32_t capacity, nagg, nnz, frozen;   /* nagg: aggregates with a node */
+    uint64_t count;         /* sum of the amounts counted */
+    uint64_t seen;          /* packets with FCGPU_R_OK */
+    uint64_t uncounted;     /* packets refused or unseen-while-frozen */
+} fcgpu_aggcount_stat;
+/* stats and read synchronise the context's device work. */
+int  fcgpu_aggcount_stats(fcgpu_ctx *ctx, fcgpu_aggcount_stat *st);
+/* write_file order: records sorted by aggregate ascending, zero counts left
+ * out. Up to max records are written (h_out may be NULL with max 0); *n gets
+ * the number available. */
+typedef struct fcgpu_aggcount_rec {
+    uint32_t agg, reserved;
+    uint64_t count;
+} fcgpu_aggcount_rec;
+int  fcgpu_aggcount_read(fcgpu_ctx *ctx, fcgpu_aggcount_rec *h_out, uint32_t max, uint32_t *n);
 
 /* Host threads the context may use for the gather / copy-out loops of
  * fcgpu_process_host (the caller's thread included; default 1). */
