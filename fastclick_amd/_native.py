@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 29
+ABI_VERSION = 30
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -155,6 +155,27 @@ class fcgpu_aggcount_rec(C.Structure):
     _fields_ = [("agg", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
 
 
+ESP_VERIFY, ESP_COMPUTE = 0, 1
+ESP_NOT_ESP, ESP_OK, ESP_BAD, ESP_NO_SA, ESP_SHORT = range(5)
+ESPAUTH_MAX_SAS = 65536
+
+
+class fcgpu_esp_sa(C.Structure):
+    _fields_ = [("spi", C.c_uint32), ("auth_key", C.c_uint8 * 16)]
+
+
+class fcgpu_espauth_config(C.Structure):
+    _fields_ = [("mode", C.c_uint32)]
+
+
+class fcgpu_esp_rec(C.Structure):
+    _fields_ = [("status", C.c_uint8), ("pad", C.c_uint8 * 3), ("icv", C.c_uint8 * 12)]
+
+
+class fcgpu_espauth_stat(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("ok", "bad", "no_sa", "too_short", "not_esp")]
+
+
 class fcgpu_out(C.Structure):
     _fields_ = [
         ("verdict", C.c_void_p),
@@ -259,6 +280,11 @@ FCGPU_SYMBOLS = {
     "fcgpu_aggcount_reset": (C.c_int, [C.c_void_p]),
     "fcgpu_aggcount_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_aggcount_stat)]),
     "fcgpu_aggcount_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fcgpu_espauth_set_sas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_espauth_configure": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espauth_config)]),
+    "fcgpu_espauth_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "fcgpu_espauth_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espauth_stat)]),
+    "fcgpu_espauth_reset": (C.c_int, [C.c_void_p]),
     "fcgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fcgpu_host_free": (None, [C.c_void_p]),
     "fcgpu_pool_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -741,6 +767,51 @@ class Context:
         rec = np.zeros(n.value, dtype=[("agg", "<u4"), ("reserved", "<u4"), ("count", "<u8")])
         self._chk(self.lib.fcgpu_aggcount_read(self.h, rec.ctypes.data, n.value, C.byref(n)), "fcgpu_aggcount_read")
         return rec["agg"][:n.value].copy(), rec["count"][:n.value].copy()
+
+    def espauth_set_sas(self, sas):
+        """ESP authentication behind the classifier (fcgpu_espauth_set_sas):
+        sas is a sequence of (spi, 16-byte key); every later process() batch
+        gets one record per packet (espauth_records). Empty: disabled."""
+        import numpy as np
+        arr = np.zeros(len(sas), dtype=[("spi", "<u4"), ("key", "u1", 16)])
+        for k, (spi, key) in enumerate(sas):
+            arr[k] = (spi, np.frombuffer(bytes(key), np.uint8))
+        self._chk(self.lib.fcgpu_espauth_set_sas(self.h, arr.ctypes.data, len(sas)), "fcgpu_espauth_set_sas")
+
+    def espauth_configure(self, mode=ESP_VERIFY):
+        ec = fcgpu_espauth_config(mode)
+        self._chk(self.lib.fcgpu_espauth_configure(self.h, C.byref(ec)), "fcgpu_espauth_configure")
+
+    def espauth_records_ptr(self) -> int:
+        p = C.c_void_p()
+        self._chk(self.lib.fcgpu_espauth_records(self.h, C.byref(p)), "fcgpu_espauth_records")
+        return p.value or 0
+
+    def espauth_records(self, n: int):
+        """The first n records of the last process() batch as a numpy
+        structured array (status u1, icv 12 x u1); synchronises the device."""
+        import numpy as np
+        import torch
+        dt = np.dtype([("status", "u1"), ("pad", "u1", 3), ("icv", "u1", 12)])
+        ptr = self.espauth_records_ptr()
+        if not ptr:
+            raise RuntimeError("espauth_records: the stage is not enabled (espauth_set_sas)")
+        if not n:
+            return np.zeros(0, dt)
+
+        class _Dev:     # the context's array, seen by torch without a copy
+            __cuda_array_interface__ = {"shape": (n * dt.itemsize,), "typestr": "|u1", "data": (ptr, False),
+                                        "version": 2}
+        torch.cuda.synchronize()
+        return torch.as_tensor(_Dev(), device="cuda").cpu().numpy().view(dt).copy()
+
+    def espauth_stats(self) -> dict:
+        st = fcgpu_espauth_stat()
+        self._chk(self.lib.fcgpu_espauth_stats(self.h, C.byref(st)), "fcgpu_espauth_stats")
+        return {k: getattr(st, k) for k, _ in fcgpu_espauth_stat._fields_}
+
+    def espauth_reset(self):
+        self._chk(self.lib.fcgpu_espauth_reset(self.h), "fcgpu_espauth_reset")
 
     def set_host_threads(self, n: int):
         self._chk(self.lib.fcgpu_set_host_threads(self.h, n), "fcgpu_set_host_threads")

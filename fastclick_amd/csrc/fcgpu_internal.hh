@@ -11,6 +11,9 @@
 //   fcgpu_exchange_api.hip  flow re-shard (fcgpu_exchange.hh)
 //   fcgpu_aggcount_api.hip  AggregateCounter: its control calls, the
 //                           post-pass and the dump (fcgpu_aggcount.hh)
+//   fcgpu_espauth_api.hip   ESP authentication (IPsecAuthHMACSHA1): its
+//                           control calls and the post-pass
+//                           (fcgpu_espauth.hh)
 // and the units without kernels:
 //   fcgpu_context.hip       open / configure / close, counters, timing,
 //                           errors, fault injection, host memory
@@ -258,6 +261,18 @@ struct fcgpu_ctx {
     uint16_t *agc_verdict = nullptr;          // [max_batch]
     uint32_t *agc_hash = nullptr;             // [max_batch]
     fcgpu_anno *agc_anno = nullptr;           // [max_batch]
+    // ESP authentication (fcgpu_espauth_set_sas, fcgpu_espauth.hh); esp_sa ==
+    // nullptr: disabled. The SA image, the records, the statistics and the
+    // per-batch scratch k_rx writes where the caller left verdict / anno NULL
+    // are one allocation group.
+    uint32_t *esp_sa = nullptr;               // [esp_nsa * 12] host/esp_sa.hh image, sorted by SPI
+    uint32_t esp_nsa = 0;
+    uint32_t esp_mode = FCGPU_ESP_VERIFY;
+    bool esp_order = true;                    // tiles ordered by block count (FCGPU_ESPAUTH_ORDER=0: arrival order)
+    uint4 *esp_rec = nullptr;                 // [max_batch] fcgpu_esp_rec of the last batch
+    unsigned long long *esp_stat = nullptr;   // [kEspStatWords]
+    uint16_t *esp_verdict = nullptr;          // [max_batch]
+    fcgpu_anno *esp_anno = nullptr;           // [max_batch]
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)
@@ -412,5 +427,12 @@ void aggcount_free(fcgpu_ctx *c);
 // and (byte modes) annotations
 hipError_t launch_aggcount(const fcgpu_ctx *c, const uint16_t *verdict, const uint32_t *hash, const fcgpu_anno *anno,
                            uint32_t n, hipStream_t s);
+
+// ---- fcgpu_espauth_api.hip --------------------------------------------------
+void espauth_free(fcgpu_ctx *c);
+// the ESP authentication post-pass (k_espauth) over one batch's frames,
+// verdicts and annotations, into c->esp_rec
+hipError_t launch_espauth(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, const uint16_t *verdict,
+                          const fcgpu_anno *anno, uint32_t n, hipStream_t s);
 
 }  // namespace fcgpu_rt

@@ -121,6 +121,33 @@ def aggcount_read(ctx: N.Context):
     return ctx.aggcount_read()
 
 
+def espauth_set_sas(ctx: N.Context, sas):
+    """ESP authentication (IPsecAuthHMACSHA1, HMAC-SHA1-96) on the device
+    behind ctx's classifier (fcgpu_espauth_set_sas): sas is a sequence of
+    (spi, 16-byte key); every later run_device batch is authenticated by the
+    k_espauth post-pass. An empty sequence disables it."""
+    ctx.espauth_set_sas(sas)
+
+
+def espauth_configure(ctx: N.Context, mode=N.ESP_VERIFY):
+    ctx.espauth_configure(mode)
+
+
+def espauth_records(ctx: N.Context, n: int):
+    """The first n records of the last run_device batch as a numpy structured
+    array (status u1, icv 12 x u1); synchronises the device."""
+    return ctx.espauth_records(n)
+
+
+def espauth_stats(ctx: N.Context) -> dict:
+    """ok, bad, no_sa, too_short, not_esp since set_sas / reset (synchronises)."""
+    return ctx.espauth_stats()
+
+
+def espauth_reset(ctx: N.Context):
+    ctx.espauth_reset()
+
+
 def process_batch(batch, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
                   program=None, program_jit=False, lb_table=None, routes=None, routes6=None, patterns=None):
     """One batch on a fresh context (see process_batches)."""

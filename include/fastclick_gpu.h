@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 29
+#define FCGPU_ABI_VERSION 30
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -810,6 +810,79 @@ typedef struct fcgpu_aggcount_rec {
     uint64_t count;
 } fcgpu_aggcount_rec;
 int  fcgpu_aggcount_read(fcgpu_ctx *ctx, fcgpu_aggcount_rec *h_out, uint32_t max, uint32_t *n);
+
+/* ESP authentication, IPsecAuthHMACSHA1 (elements/ipsec/hmacsha1.cc:61-96)
+ * behind the classifier: HMAC-SHA1 with the SA's 16-byte key (hmac.cc:147-159,
+ * plain HMAC), truncated to 96 bits, in both of the element's modes. It is
+ * the authentication stage of the inbound chain of conf/router/
+ * ipsec-router.click, rt[0] -> StripIPHeader -> IPsecAES(0) ->
+ * IPsecAuthHMACSHA1(1) -> IPsecESPUnencap; the stage authenticates whatever
+ * bytes the frame holds, exactly as the element does (the reference chain
+ * decrypts first). Per packet:
+ *   - it is considered iff its verdict reason is FCGPU_R_OK, anno.ipver == 4
+ *     and the IP protocol byte (frame byte nh + 9) is 50, the ESP case of
+ *     IPsecRouteTable::push (ipsecroutetable.cc:217-237); any other packet is
+ *     left alone, status FCGPU_ESP_NOT_ESP;
+ *   - e0 = nh + 4 * ihl (the bytes StripIPHeader removes), end = anno.length
+ *     (after CheckIPHeader's trim), elen = end - e0;
+ *   - elen < 16 + 12, the esp_new header (esp.hh:26-30) plus the digest:
+ *     FCGPU_ESP_SHORT. (The reference would hand HMAC length() - 12 < 0; this
+ *     library defines the case as a status);
+ *   - the SA is found by the SPI, the big-endian word at e0 (IPsecESPEncap
+ *     wrote it from the SA the annotation names); none: FCGPU_ESP_NO_SA, the
+ *     reference's "Invalid SPI, Dropping packet";
+ *   - FCGPU_ESP_VERIFY: the digest is HMAC-SHA1(auth_key, frame[e0, end - 12));
+ *     its first 12 bytes are compared with frame[end - 12, end): FCGPU_ESP_OK
+ *     or FCGPU_ESP_BAD; the record's icv holds the computed 12 bytes;
+ *   - FCGPU_ESP_COMPUTE: icv = the first 12 bytes of HMAC-SHA1(auth_key,
+ *     frame[e0, end)), the bytes put(12) would append; FCGPU_ESP_OK.
+ * Frames are never written; verdict, hash, the partition and the counters are
+ * untouched. Out of scope: IPsecAES, IPsecESPUnencap, anti-replay and the
+ * element keyword.
+ * The stage is a post-pass kernel behind k_rx on the batch's stream (DESIGN.md
+ * 3.10). Its records are one context-owned array of max_batch entries holding
+ * the last fcgpu_process batch; where the caller leaves fcgpu_out.verdict or
+ * anno NULL, k_rx writes context scratch instead (allocated with the table and
+ * the records as one group: a failed fcgpu_espauth_set_sas leaves the
+ * installed table in place). Served by fcgpu_process, on one stream per
+ * context; while SAs are installed fcgpu_process_jobs, fcgpu_process_host,
+ * fcgpu_process_counted, fcgpu_process_mbufs, fcgpu_span_submit and
+ * fcgpu_span_submit_block return FCGPU_EINVAL. */
+#define FCGPU_ESP_VERIFY  0u
+#define FCGPU_ESP_COMPUTE 1u
+#define FCGPU_ESP_NOT_ESP 0
+#define FCGPU_ESP_OK      1
+#define FCGPU_ESP_BAD     2
+#define FCGPU_ESP_NO_SA   3
+#define FCGPU_ESP_SHORT   4
+#define FCGPU_ESPAUTH_MAX_SAS 65536u
+typedef struct fcgpu_esp_sa {
+    uint32_t spi;           /* host order; never 0 */
+    uint8_t auth_key[16];
+} fcgpu_esp_sa;
+typedef struct fcgpu_espauth_config {
+    uint32_t mode;          /* FCGPU_ESP_VERIFY | FCGPU_ESP_COMPUTE */
+} fcgpu_espauth_config;
+typedef struct fcgpu_esp_rec {
+    uint8_t status;         /* FCGPU_ESP_* */
+    uint8_t pad[3];
+    uint8_t icv[12];        /* FCGPU_ESP_OK / _BAD: the computed digest; else 0 */
+} fcgpu_esp_rec;
+typedef struct fcgpu_espauth_stat {
+    uint64_t ok, bad, no_sa, too_short, not_esp;
+} fcgpu_espauth_stat;
+/* Replaces the SA table (the statistics restart, the mode stays); n == 0
+ * disables the stage and frees it. FCGPU_EINVAL: SPI 0, a duplicate SPI, more
+ * than FCGPU_ESPAUTH_MAX_SAS. Synchronises the device. */
+int  fcgpu_espauth_set_sas(fcgpu_ctx *ctx, const fcgpu_esp_sa *sas, uint32_t n);
+/* The mode of the batches submitted after this call (default VERIFY). */
+int  fcgpu_espauth_configure(fcgpu_ctx *ctx, const fcgpu_espauth_config *cfg);
+/* Device pointer to the records, [max_batch]: entry i is packet i of the last
+ * fcgpu_process batch, ordered behind it on its stream. NULL while disabled. */
+int  fcgpu_espauth_records(fcgpu_ctx *ctx, const fcgpu_esp_rec **d_rec);
+/* Packets per status since set_sas / reset. Synchronises the device. */
+int  fcgpu_espauth_stats(fcgpu_ctx *ctx, fcgpu_espauth_stat *st);
+int  fcgpu_espauth_reset(fcgpu_ctx *ctx);
 
 /* Host threads the context may use for the gather / copy-out loops of
  * fcgpu_process_host (the caller's thread included; default 1). */

@@ -193,6 +193,11 @@ int fcgpu_aggcount_freeze(fcgpu_ctx *, int) { return FCGPU_OK; }
 int fcgpu_aggcount_reset(fcgpu_ctx *) { return FCGPU_OK; }
 int fcgpu_aggcount_stats(fcgpu_ctx *, fcgpu_aggcount_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
 int fcgpu_aggcount_read(fcgpu_ctx *, fcgpu_aggcount_rec *, uint32_t, uint32_t *n) { *n = 0; return FCGPU_OK; }
+int fcgpu_espauth_set_sas(fcgpu_ctx *, const fcgpu_esp_sa *, uint32_t) { return FCGPU_OK; }
+int fcgpu_espauth_configure(fcgpu_ctx *, const fcgpu_espauth_config *) { return FCGPU_OK; }
+int fcgpu_espauth_records(fcgpu_ctx *, const fcgpu_esp_rec **d) { *d = nullptr; return FCGPU_OK; }
+int fcgpu_espauth_stats(fcgpu_ctx *, fcgpu_espauth_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
+int fcgpu_espauth_reset(fcgpu_ctx *) { return FCGPU_OK; }
 int fcgpu_lb_hash_ring(uint32_t nsel, uint32_t size, uint8_t *out) {
     for (uint32_t i = 0; i < size; ++i) out[i] = (uint8_t)(nsel ? i % nsel : 0);
     return FCGPU_OK;
