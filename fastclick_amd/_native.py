@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 30
+ABI_VERSION = 31
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -176,6 +176,18 @@ class fcgpu_espauth_stat(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("ok", "bad", "no_sa", "too_short", "not_esp")]
 
 
+ESP_UNALIGNED = 5
+ESPAES_MAX_SAS = 65536
+
+
+class fcgpu_espaes_sa(C.Structure):
+    _fields_ = [("spi", C.c_uint32), ("enc_key", C.c_uint8 * 16)]
+
+
+class fcgpu_espaes_stat(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("ok", "no_sa", "too_short", "unaligned", "not_esp", "blocks")]
+
+
 class fcgpu_out(C.Structure):
     _fields_ = [
         ("verdict", C.c_void_p),
@@ -285,6 +297,10 @@ FCGPU_SYMBOLS = {
     "fcgpu_espauth_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "fcgpu_espauth_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espauth_stat)]),
     "fcgpu_espauth_reset": (C.c_int, [C.c_void_p]),
+    "fcgpu_espaes_set_sas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_espaes_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "fcgpu_espaes_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espaes_stat)]),
+    "fcgpu_espaes_reset": (C.c_int, [C.c_void_p]),
     "fcgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fcgpu_host_free": (None, [C.c_void_p]),
     "fcgpu_pool_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -812,6 +828,46 @@ class Context:
 
     def espauth_reset(self):
         self._chk(self.lib.fcgpu_espauth_reset(self.h), "fcgpu_espauth_reset")
+
+    def espaes_set_sas(self, sas):
+        """ESP decryption in front of the authentication stage
+        (fcgpu_espaes_set_sas): sas is a sequence of (spi, 16-byte AES key);
+        every later process() batch is decrypted IN PLACE in its arena and
+        gets one status byte per packet (espaes_status). Empty: disabled."""
+        import numpy as np
+        arr = np.zeros(len(sas), dtype=[("spi", "<u4"), ("key", "u1", 16)])
+        for k, (spi, key) in enumerate(sas):
+            arr[k] = (spi, np.frombuffer(bytes(key), np.uint8))
+        self._chk(self.lib.fcgpu_espaes_set_sas(self.h, arr.ctypes.data, len(sas)), "fcgpu_espaes_set_sas")
+
+    def espaes_status_ptr(self) -> int:
+        p = C.c_void_p()
+        self._chk(self.lib.fcgpu_espaes_status(self.h, C.byref(p)), "fcgpu_espaes_status")
+        return p.value or 0
+
+    def espaes_status(self, n: int):
+        """The first n status bytes (ESP_*) of the last process() batch as a
+        numpy array; synchronises the device."""
+        import numpy as np
+        import torch
+        ptr = self.espaes_status_ptr()
+        if not ptr:
+            raise RuntimeError("espaes_status: the stage is not enabled (espaes_set_sas)")
+        if not n:
+            return np.zeros(0, np.uint8)
+
+        class _Dev:     # the context's array, seen by torch without a copy
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+        torch.cuda.synchronize()
+        return torch.as_tensor(_Dev(), device="cuda").cpu().numpy().copy()
+
+    def espaes_stats(self) -> dict:
+        st = fcgpu_espaes_stat()
+        self._chk(self.lib.fcgpu_espaes_stats(self.h, C.byref(st)), "fcgpu_espaes_stats")
+        return {k: getattr(st, k) for k, _ in fcgpu_espaes_stat._fields_}
+
+    def espaes_reset(self):
+        self._chk(self.lib.fcgpu_espaes_reset(self.h), "fcgpu_espaes_reset")
 
     def set_host_threads(self, n: int):
         self._chk(self.lib.fcgpu_set_host_threads(self.h, n), "fcgpu_set_host_threads")

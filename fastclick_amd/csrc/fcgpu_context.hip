@@ -193,6 +193,7 @@ void fcgpu_close(fcgpu_ctx *c) {
         flow_free(c);
         aggcount_free(c);
         espauth_free(c);
+        espaes_free(c);
         hipFree(c->d_mptr);
         hipFree(c->d_mdesc);
         hipFree(c->x_bsum);

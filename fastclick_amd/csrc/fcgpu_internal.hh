@@ -14,6 +14,8 @@
 //   fcgpu_espauth_api.hip   ESP authentication (IPsecAuthHMACSHA1): its
 //                           control calls and the post-pass
 //                           (fcgpu_espauth.hh)
+//   fcgpu_espaes_api.hip    ESP decryption (IPsecAES(0)): its control calls
+//                           and the post-pass (fcgpu_espaes.hh)
 // and the units without kernels:
 //   fcgpu_context.hip       open / configure / close, counters, timing,
 //                           errors, fault injection, host memory
@@ -273,6 +275,16 @@ struct fcgpu_ctx {
     unsigned long long *esp_stat = nullptr;   // [kEspStatWords]
     uint16_t *esp_verdict = nullptr;          // [max_batch]
     fcgpu_anno *esp_anno = nullptr;           // [max_batch]
+    // ESP decryption (fcgpu_espaes_set_sas, fcgpu_espaes.hh); aes_sa ==
+    // nullptr: disabled. One allocation group, as above.
+    uint32_t *aes_sa = nullptr;               // Td0[256], inverse S-box[64 words], then [aes_nsa * 48] host/aes_key.hh image
+    uint32_t aes_nsa = 0;
+    uint32_t aes_ntab = 1, aes_repl = 1;      // tables and replicas in LDS (FCGPU_ESPAES_TABLES / _REPLICAS)
+    uint32_t aes_tile = 0;                    // packets per tile; 0: by the batch's size (FCGPU_ESPAES_TILE)
+    uint8_t *aes_status = nullptr;            // [max_batch] FCGPU_ESP_* of the last batch
+    unsigned long long *aes_stat = nullptr;   // [kAesStatWords]
+    uint16_t *aes_verdict = nullptr;          // [max_batch]
+    fcgpu_anno *aes_anno = nullptr;           // [max_batch]
     uint32_t prog_n = 0, prog_kind = 0, prog_q = 0, prog_tab = 0;
     int32_t prog_all = -1;
     std::vector<fcgpu_step> prog_host;   // the installed program (capture reach)
@@ -434,5 +446,12 @@ void espauth_free(fcgpu_ctx *c);
 // verdicts and annotations, into c->esp_rec
 hipError_t launch_espauth(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, const uint16_t *verdict,
                           const fcgpu_anno *anno, uint32_t n, hipStream_t s);
+
+// ---- fcgpu_espaes_api.hip ---------------------------------------------------
+void espaes_free(fcgpu_ctx *c);
+// the ESP decryption post-pass (k_espaes) over one batch: it WRITES the
+// frames of `arena` in place and c->aes_status
+hipError_t launch_espaes(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, const uint16_t *verdict,
+                         const fcgpu_anno *anno, uint32_t n, hipStream_t s);
 
 }  // namespace fcgpu_rt

@@ -87,6 +87,13 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
         if (!a.verdict) a.verdict = c->esp_verdict;
         if (!a.anno) a.anno = c->esp_anno;
     }
+    if (c->aes_sa) {    // and the ESP decryption stage, which also writes the arena
+        if (layout) return fail(c, FCGPU_EINVAL, "the ESP decryption stage reads {off, len} descriptors and fcgpu_anno "
+                                                 "records (public layouts only)");
+        if (n_dev) return fail(c, FCGPU_EINVAL, "the ESP decryption stage takes the host's packet count");
+        if (!a.verdict) a.verdict = c->aes_verdict;
+        if (!a.anno) a.anno = c->aes_anno;
+    }
     a.tilecnt = c->d_tilecnt;
     a.perm = o->perm;
     a.tile_count = o->tile_count;
@@ -128,6 +135,7 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
                             timed ? ev[0].b : nullptr, c->jit_src.empty() ? nullptr : c));
     HIPCHK(c, hipGetLastError());
     if (c->agc_tab) HIPCHK(c, launch_aggcount(c, a.verdict, a.hash, a.anno, n, s));
+    if (c->aes_sa) HIPCHK(c, launch_espaes(c, d_arena, d_desc, a.verdict, a.anno, n, s));   // in front: espauth reads plaintext
     if (c->esp_sa) HIPCHK(c, launch_espauth(c, d_arena, d_desc, a.verdict, a.anno, n, s));
     if (a.fl.slots) {   // the batch's new flows get their IDs (fcgpu_flow.hh)
         HIPCHK(c, flow_pass(c, a.fl, n, s));
@@ -680,6 +688,8 @@ int fcgpu_process_counted(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: the aggregate counter's post-pass takes the host's packet count");
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: the ESP decryption stage is served by fcgpu_process");
     // the whole-batch partition's scan and scatter take the host's n
     if (o->partition == FCGPU_PART_GLOBAL && (o->perm || o->port_start))
         return fail(c, FCGPU_EINVAL, "fcgpu_process_counted: no whole-batch partition (FCGPU_PART_GLOBAL)");
@@ -694,6 +704,8 @@ int fcgpu_process_jobs(fcgpu_ctx *c, const fcgpu_job *jobs, uint32_t njobs, void
     // its records are one array per context: the last batch's
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_jobs: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_jobs: the ESP decryption stage is served by fcgpu_process");
     // every job is checked before any is launched: a bad job launches nothing
     bool split = false;
     for (uint32_t k = 0; k < njobs; ++k) {
@@ -755,6 +767,8 @@ int fcgpu_process_host(fcgpu_ctx *c, const uint8_t *const *frames, const uint32_
         return fail(c, FCGPU_EINVAL, "fcgpu_process_host: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_host: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_host: the ESP decryption stage is served by fcgpu_process");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (n == 0) return FCGPU_OK;
     if (h->partition > FCGPU_PART_TILE) return fail(c, FCGPU_EINVAL, "bad partition mode");
@@ -823,6 +837,8 @@ int fcgpu_process_mbufs(fcgpu_ctx *c, void *const *mbufs, uint32_t n, const fcgp
         return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: the ESP decryption stage is served by fcgpu_process");
     if (!c->pool_host) return fail(c, FCGPU_EINVAL, "fcgpu_process_mbufs: no pool registered (fcgpu_pool_register)");
     if (L->header_bytes > 64 || L->buf_addr + 8 > L->header_bytes || L->data_off + 2 > L->header_bytes ||
         L->data_len + 2 > L->header_bytes || (L->buf_addr & 7) || (L->data_off & 1) || (L->data_len & 1))

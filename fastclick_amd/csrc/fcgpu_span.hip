@@ -411,6 +411,8 @@ int fcgpu_span_submit(fcgpu_ctx *c, uint32_t slot, const uint8_t *h_span, size_t
         return fail(c, FCGPU_EINVAL, "fcgpu_span_submit: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_span_submit: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_span_submit: the ESP decryption stage is served by fcgpu_process");
     if (n > c->max_batch) return fail(c, FCGPU_ENOMEM, "batch larger than max_batch");
     if (bytes > 0xffffffffull - kArenaPad) return fail(c, FCGPU_EINVAL, "span larger than 4 GiB");
     SpanSlot &sp = c->span[slot];
@@ -693,6 +695,8 @@ int fcgpu_span_submit_block(fcgpu_ctx *c, uint32_t slot, const void *h_in, size_
                     "fcgpu_span_submit_block: the aggregate counter is served by fcgpu_process and fcgpu_process_jobs");
     if (c->esp_sa)
         return fail(c, FCGPU_EINVAL, "fcgpu_span_submit_block: the ESP authentication stage is served by fcgpu_process");
+    if (c->aes_sa)
+        return fail(c, FCGPU_EINVAL, "fcgpu_span_submit_block: the ESP decryption stage is served by fcgpu_process");
     const bool force_copy = (outputs & FCGPU_SUBMIT_COPY) != 0;
     const bool desc32 = (outputs & FCGPU_SUBMIT_DESC32) != 0;
     outputs &= ~(FCGPU_SUBMIT_COPY | FCGPU_SUBMIT_DESC32);

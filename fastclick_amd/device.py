@@ -148,6 +148,29 @@ def espauth_reset(ctx: N.Context):
     ctx.espauth_reset()
 
 
+def espaes_set_sas(ctx: N.Context, sas):
+    """ESP decryption (IPsecAES(0), AES-128 in the element's 8-byte-IV
+    chaining) on the device in front of the authentication stage
+    (fcgpu_espaes_set_sas): sas is a sequence of (spi, 16-byte key); every later
+    run_device batch is decrypted in place in its arena by the k_espaes
+    post-pass. An empty sequence disables it."""
+    ctx.espaes_set_sas(sas)
+
+
+def espaes_status(ctx: N.Context, n: int):
+    """The first n status bytes of the last run_device batch; synchronises."""
+    return ctx.espaes_status(n)
+
+
+def espaes_stats(ctx: N.Context) -> dict:
+    """ok, no_sa, too_short, unaligned, not_esp, blocks since set_sas / reset."""
+    return ctx.espaes_stats()
+
+
+def espaes_reset(ctx: N.Context):
+    ctx.espaes_reset()
+
+
 def process_batch(batch, cfg, *, anno=True, perm=True, device_index=0, partition=N.PART_GLOBAL,
                   program=None, program_jit=False, lb_table=None, routes=None, routes6=None, patterns=None):
     """One batch on a fresh context (see process_batches)."""

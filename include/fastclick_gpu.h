@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 30
+#define FCGPU_ABI_VERSION 31
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -837,8 +837,10 @@ int  fcgpu_aggcount_read(fcgpu_ctx *ctx, fcgpu_aggcount_rec *h_out, uint32_t max
  *   - FCGPU_ESP_COMPUTE: icv = the first 12 bytes of HMAC-SHA1(auth_key,
  *     frame[e0, end)), the bytes put(12) would append; FCGPU_ESP_OK.
  * Frames are never written; verdict, hash, the partition and the counters are
- * untouched. Out of scope: IPsecAES, IPsecESPUnencap, anti-replay and the
- * element keyword.
+ * untouched. Out of scope: IPsecESPUnencap, anti-replay and the element
+ * keyword. With the decryption stage below installed as well, k_espaes runs
+ * in front of this stage on the same stream, so the digest is taken over the
+ * decrypted bytes, as in the reference's chain.
  * The stage is a post-pass kernel behind k_rx on the batch's stream (DESIGN.md
  * 3.10). Its records are one context-owned array of max_batch entries holding
  * the last fcgpu_process batch; where the caller leaves fcgpu_out.verdict or
@@ -883,6 +885,64 @@ int  fcgpu_espauth_records(fcgpu_ctx *ctx, const fcgpu_esp_rec **d_rec);
 /* Packets per status since set_sas / reset. Synchronises the device. */
 int  fcgpu_espauth_stats(fcgpu_ctx *ctx, fcgpu_espauth_stat *st);
 int  fcgpu_espauth_reset(fcgpu_ctx *ctx);
+
+/* ESP decryption, IPsecAES(0) (elements/ipsec/aes.cc:69-138, decrypt branch)
+ * behind the classifier and in front of the authentication stage above:
+ * AES-128 (FIPS 197) with the SA's 16-byte key in the element's 8-byte-IV
+ * chaining, in place in the arena. Per packet:
+ *   - it is considered by the rule of the authentication stage: verdict
+ *     reason FCGPU_R_OK, anno.ipver == 4 and frame byte nh + 9 == 50; any
+ *     other packet: FCGPU_ESP_NOT_ESP, no byte touched;
+ *   - e0 = nh + 4 * ihl, end = anno.length, elen = end - e0; elen < 28:
+ *     FCGPU_ESP_SHORT; the SA is found by the big-endian SPI at e0, none:
+ *     FCGPU_ESP_NO_SA;
+ *   - plen = elen - 16 - 12 (esp_new and the element's _ignore = 12);
+ *     plen % 8 != 0: FCGPU_ESP_UNALIGNED, no byte touched (the reference's
+ *     loop would run past the packet's end; this library defines the case);
+ *   - plen % 16 == 8: plen += 8 -- the reference encrypts the first 8 digest
+ *     bytes rather than pad, so the region still ends inside the frame;
+ *   - nblk = plen / 16 (may be 0); block i is C_i = frame[e0 + 16 + 16 i,
+ *     + 16); it becomes P_i = AES128-decrypt(enc_key, C_i) with its FIRST 8
+ *     BYTES ONLY XORed with IV = frame[e0 + 8, e0 + 16) for i = 0 and with
+ *     the first 8 bytes of the ciphertext C_{i-1} otherwise; bytes 8..15 are
+ *     the raw block decryption. This is the element's chaining, not RFC 3602
+ *     CBC. The IV field is unchanged (the reference restores it);
+ *     FCGPU_ESP_OK.
+ * The stage writes exactly the 16 * nblk bytes of every OK packet: no header,
+ * IV or untouched digest byte, no byte of another packet, no slack byte
+ * between frames. WHILE A TABLE IS INSTALLED fcgpu_process WRITES d_arena
+ * (the element decrypts in place after uniqueify()); the parameter stays
+ * const in the signature. Loads may over-read within the 16-byte slack.
+ * One status byte per packet in a context-owned device array of max_batch
+ * entries holding the last fcgpu_process batch. The table, the status array,
+ * the statistics and the scratch k_rx writes where fcgpu_out.verdict or anno
+ * is NULL are one allocation group: a failed fcgpu_espaes_set_sas leaves the
+ * installed table in place. Launch order on the batch's stream: k_rx, the
+ * aggregate counter, k_espaes, k_espauth, the flow pass.
+ * Served by fcgpu_process; while SAs are installed fcgpu_process_jobs,
+ * fcgpu_process_host, fcgpu_process_counted, fcgpu_process_mbufs,
+ * fcgpu_span_submit and fcgpu_span_submit_block return FCGPU_EINVAL. Out of
+ * scope: IPsecAES(1) (encryption), IPsecESPUnencap, anti-replay, the element
+ * keyword. */
+#define FCGPU_ESP_UNALIGNED 5
+#define FCGPU_ESPAES_MAX_SAS 65536u
+typedef struct fcgpu_espaes_sa {
+    uint32_t spi;           /* host order; never 0 */
+    uint8_t enc_key[16];
+} fcgpu_espaes_sa;
+typedef struct fcgpu_espaes_stat {
+    uint64_t ok, no_sa, too_short, unaligned, not_esp, blocks;   /* blocks: 16-byte blocks decrypted */
+} fcgpu_espaes_stat;
+/* Replaces the SA table (the statistics restart); n == 0 disables the stage
+ * and frees it. FCGPU_EINVAL: SPI 0, a duplicate SPI, more than
+ * FCGPU_ESPAES_MAX_SAS. Synchronises the device. */
+int  fcgpu_espaes_set_sas(fcgpu_ctx *ctx, const fcgpu_espaes_sa *sas, uint32_t n);
+/* Device pointer to the status bytes (FCGPU_ESP_*), [max_batch]: entry i is
+ * packet i of the last fcgpu_process batch. NULL while disabled. */
+int  fcgpu_espaes_status(fcgpu_ctx *ctx, const uint8_t **d_status);
+/* Packets per status and blocks since set_sas / reset. Synchronises the device. */
+int  fcgpu_espaes_stats(fcgpu_ctx *ctx, fcgpu_espaes_stat *st);
+int  fcgpu_espaes_reset(fcgpu_ctx *ctx);
 
 /* Host threads the context may use for the gather / copy-out loops of
  * fcgpu_process_host (the caller's thread included; default 1). */

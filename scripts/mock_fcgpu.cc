@@ -198,6 +198,10 @@ int fcgpu_espauth_configure(fcgpu_ctx *, const fcgpu_espauth_config *) { return 
 int fcgpu_espauth_records(fcgpu_ctx *, const fcgpu_esp_rec **d) { *d = nullptr; return FCGPU_OK; }
 int fcgpu_espauth_stats(fcgpu_ctx *, fcgpu_espauth_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
 int fcgpu_espauth_reset(fcgpu_ctx *) { return FCGPU_OK; }
+int fcgpu_espaes_set_sas(fcgpu_ctx *, const fcgpu_espaes_sa *, uint32_t) { return FCGPU_OK; }
+int fcgpu_espaes_status(fcgpu_ctx *, const uint8_t **d) { *d = nullptr; return FCGPU_OK; }
+int fcgpu_espaes_stats(fcgpu_ctx *, fcgpu_espaes_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
+int fcgpu_espaes_reset(fcgpu_ctx *) { return FCGPU_OK; }
 int fcgpu_lb_hash_ring(uint32_t nsel, uint32_t size, uint8_t *out) {
     for (uint32_t i = 0; i < size; ++i) out[i] = (uint8_t)(nsel ? i % nsel : 0);
     return FCGPU_OK;
