@@ -15,7 +15,7 @@ LIBFCGPU = os.environ.get("FCGPU_LIB") or os.path.join(LIB_DIR, "libfcgpu.so")
 LIBFCCLICK = os.path.join(LIB_DIR, "libfcclick.so")
 
 # ---- constants mirrored from include/fastclick_gpu.h -----------------------
-ABI_VERSION = 31
+ABI_VERSION = 32
 SPAN_SLOTS = 3
 SPAN_COPY = 0
 SPAN_ZEROCOPY = 1
@@ -155,7 +155,7 @@ class fcgpu_aggcount_rec(C.Structure):
     _fields_ = [("agg", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64)]
 
 
-ESP_VERIFY, ESP_COMPUTE = 0, 1
+ESP_VERIFY, ESP_COMPUTE, ESP_SEAL = 0, 1, 2
 ESP_NOT_ESP, ESP_OK, ESP_BAD, ESP_NO_SA, ESP_SHORT = range(5)
 ESPAUTH_MAX_SAS = 65536
 
@@ -178,10 +178,15 @@ class fcgpu_espauth_stat(C.Structure):
 
 ESP_UNALIGNED = 5
 ESPAES_MAX_SAS = 65536
+ESPAES_DECRYPT, ESPAES_ENCRYPT = 0, 1
 
 
 class fcgpu_espaes_sa(C.Structure):
     _fields_ = [("spi", C.c_uint32), ("enc_key", C.c_uint8 * 16)]
+
+
+class fcgpu_espaes_config(C.Structure):
+    _fields_ = [("mode", C.c_uint32)]
 
 
 class fcgpu_espaes_stat(C.Structure):
@@ -298,6 +303,7 @@ FCGPU_SYMBOLS = {
     "fcgpu_espauth_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espauth_stat)]),
     "fcgpu_espauth_reset": (C.c_int, [C.c_void_p]),
     "fcgpu_espaes_set_sas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "fcgpu_espaes_configure": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espaes_config)]),
     "fcgpu_espaes_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "fcgpu_espaes_stats": (C.c_int, [C.c_void_p, C.POINTER(fcgpu_espaes_stat)]),
     "fcgpu_espaes_reset": (C.c_int, [C.c_void_p]),
@@ -839,6 +845,13 @@ class Context:
         for k, (spi, key) in enumerate(sas):
             arr[k] = (spi, np.frombuffer(bytes(key), np.uint8))
         self._chk(self.lib.fcgpu_espaes_set_sas(self.h, arr.ctypes.data, len(sas)), "fcgpu_espaes_set_sas")
+
+    def espaes_configure(self, mode=ESPAES_DECRYPT):
+        """ESPAES_DECRYPT (k_espaes in front of the authentication stage) or
+        ESPAES_ENCRYPT (k_espenc behind it: with espauth_configure(ESP_SEAL)
+        one process() call seals and encrypts) for the batches that follow."""
+        ec = fcgpu_espaes_config(mode)
+        self._chk(self.lib.fcgpu_espaes_configure(self.h, C.byref(ec)), "fcgpu_espaes_configure")
 
     def espaes_status_ptr(self) -> int:
         p = C.c_void_p()

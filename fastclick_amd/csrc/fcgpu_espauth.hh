@@ -8,8 +8,11 @@
 // 217-237). With e0 = nh + 4 * ihl, end = anno.length, elen = end - e0:
 // SHORT if elen < 28, NO_SA if the SPI (big-endian word at e0) is not in the
 // table; VERIFY hashes L = elen - 12 bytes from e0 and compares 12 digest
-// bytes with the frame's last 12, COMPUTE hashes L = elen bytes. One 16-byte
-// record per packet at the packet's own index; frames are never written.
+// bytes with the frame's last 12, COMPUTE hashes L = elen bytes, SEAL hashes
+// as VERIFY and writes the 12 digest bytes to the frame's last 12 (the
+// outbound IPsecAuthHMACSHA1(0) on a frame that holds the room). One 16-byte
+// record per packet at the packet's own index; VERIFY and COMPUTE never
+// write frames.
 //
 // SHA-1 over one message is a serial chain, so the parallelism is across
 // packets: one lane per packet, 256 packets per tile, a workgroup looping
@@ -73,7 +76,7 @@ struct EspArgs {
     const uint16_t *verdict;      // [n] k_rx's verdicts
     const uint32_t *anno;         // [n] fcgpu_anno as 4 words each
     uint32_t n, ntiles;
-    uint32_t mode;                // FCGPU_ESP_VERIFY / FCGPU_ESP_COMPUTE
+    uint32_t mode;                // FCGPU_ESP_VERIFY / FCGPU_ESP_COMPUTE / FCGPU_ESP_SEAL (which writes the arena)
     const uint32_t *sa;           // [nsa * kEspSaWords], sorted by spi
     uint32_t nsa;                 // >= 1
     uint32_t sa_lds;              // the image is staged in (dynamic) LDS
@@ -127,6 +130,36 @@ __device__ __forceinline__ void sha1_block(uint32_t (&h)[5], uint32_t (&w)[16], 
 }
 #undef FCGPU_SHA1_STEP
 #undef FCGPU_SHA1_W
+
+// SEAL: the 12 digest bytes (three little-endian words) to arena + at,
+// whatever its alignment, by naturally aligned stores of own bytes only: a
+// head of 0-3 bytes (byte / short), two or three dwords, a tail.
+__device__ __forceinline__ void esp_store12(uint8_t *arena, size_t at, uint32_t w0, uint32_t w1, uint32_t w2) {
+    uint8_t *p = arena + at;
+    const uint32_t m = (uint32_t)at & 3u;
+    if (m == 0) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+        q[0] = w0;
+        q[1] = w1;
+        q[2] = w2;
+        return;
+    }
+    // head: 4 - m bytes
+    if (m & 1u) *p = (uint8_t)w0;
+    if (m == 1u) *reinterpret_cast<uint16_t *>(p + 1) = (uint16_t)(w0 >> 8);
+    if (m == 2u) *reinterpret_cast<uint16_t *>(p) = (uint16_t)w0;
+    uint32_t *q = reinterpret_cast<uint32_t *>(p + 4 - m);
+    q[0] = __builtin_amdgcn_alignbyte(w1, w0, 4u - m);
+    q[1] = __builtin_amdgcn_alignbyte(w2, w1, 4u - m);
+    // tail: m bytes, the top of w2
+    uint8_t *e = p + 12 - m;
+    if (m == 1u) *e = (uint8_t)(w2 >> 24);
+    if (m == 2u) *reinterpret_cast<uint16_t *>(e) = (uint16_t)(w2 >> 16);
+    if (m == 3u) {
+        *reinterpret_cast<uint16_t *>(e) = (uint16_t)(w2 >> 8);
+        e[2] = (uint8_t)(w2 >> 24);
+    }
+}
 
 // The wave's gather of segment `seg` (64 B per packet) into buf (4 KB): lane l
 // of instruction k fetches chunk (l & 3) ^ swizzle of slot wbase + 16k + l/4,
@@ -329,6 +362,8 @@ __global__ __launch_bounds__(kTile) void k_espauth(const EspArgs A) {
         }
         const uint32_t oi = tile * kTile + mlane;
         if (oi < A.n) A.rec[oi] = mhashed ? make_uint4(st, i0, i1, i2) : make_uint4(st, 0u, 0u, 0u);
+        if (mhashed && A.mode == FCGPU_ESP_SEAL)   // frame[end - 12, end): where VERIFY reads
+            esp_store12(const_cast<uint8_t *>(A.arena), (size_t)M.x + rb + mL, i0, i1, i2);
         // ---- 8. statistics -------------------------------------------------
         const bool mlive = oi < A.n;
         cnt[0] += (uint32_t)__popcll(__ballot(mlive && st == FCGPU_ESP_OK));

@@ -44,7 +44,7 @@ hipError_t launch_espauth(const fcgpu_ctx *c, const uint8_t *arena, const uint32
         return hipErrorInvalidValue;
     if (!n) return hipSuccess;
     EspArgs a;
-    a.arena = arena;
+    a.arena = arena;              // FCGPU_ESP_SEAL writes the digests into it (include/fastclick_gpu.h)
     a.desc = reinterpret_cast<const uint2 *>(desc);
     a.verdict = verdict;
     a.anno = reinterpret_cast<const uint32_t *>(anno);
@@ -116,7 +116,7 @@ int fcgpu_espauth_set_sas(fcgpu_ctx *c, const fcgpu_esp_sa *sas, uint32_t n) {
 
 int fcgpu_espauth_configure(fcgpu_ctx *c, const fcgpu_espauth_config *cfg) {
     if (!c || !cfg) return FCGPU_EINVAL;
-    if (cfg->mode > FCGPU_ESP_COMPUTE) return fail(c, FCGPU_EINVAL, "fcgpu_espauth_configure: bad mode");
+    if (cfg->mode > FCGPU_ESP_SEAL) return fail(c, FCGPU_EINVAL, "fcgpu_espauth_configure: bad mode");
     c->esp_mode = cfg->mode;      // the next batch's launch takes it
     return FCGPU_OK;
 }

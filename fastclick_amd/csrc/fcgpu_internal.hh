@@ -14,8 +14,9 @@
 //   fcgpu_espauth_api.hip   ESP authentication (IPsecAuthHMACSHA1): its
 //                           control calls and the post-pass
 //                           (fcgpu_espauth.hh)
-//   fcgpu_espaes_api.hip    ESP decryption (IPsecAES(0)): its control calls
-//                           and the post-pass (fcgpu_espaes.hh)
+//   fcgpu_espaes_api.hip    ESP decryption and encryption (IPsecAES(0) / (1)):
+//                           the control calls and the post-passes
+//                           (fcgpu_espaes.hh, fcgpu_espenc.hh)
 // and the units without kernels:
 //   fcgpu_context.hip       open / configure / close, counters, timing,
 //                           errors, fault injection, host memory
@@ -275,10 +276,14 @@ struct fcgpu_ctx {
     unsigned long long *esp_stat = nullptr;   // [kEspStatWords]
     uint16_t *esp_verdict = nullptr;          // [max_batch]
     fcgpu_anno *esp_anno = nullptr;           // [max_batch]
-    // ESP decryption (fcgpu_espaes_set_sas, fcgpu_espaes.hh); aes_sa ==
-    // nullptr: disabled. One allocation group, as above.
-    uint32_t *aes_sa = nullptr;               // Td0[256], inverse S-box[64 words], then [aes_nsa * 48] host/aes_key.hh image
+    // ESP decryption / encryption (fcgpu_espaes_set_sas, fcgpu_espaes.hh,
+    // fcgpu_espenc.hh); aes_sa == nullptr: disabled. One allocation group, as
+    // above.
+    uint32_t *aes_sa = nullptr;               // Td0[256], inverse S-box[64 words], [aes_nsa * 48] host/aes_key.hh image,
+                                              // then the encryption image [aes_nsa * 48] and Te0[256]
     uint32_t aes_nsa = 0;
+    uint32_t aes_mode = FCGPU_ESPAES_DECRYPT; // fcgpu_espaes_configure: k_espaes in front of k_espauth / k_espenc behind it
+    bool aes_order = true;                    // k_espenc's tiles ordered by nblk (FCGPU_ESPENC_ORDER=0: arrival order)
     uint32_t aes_ntab = 1, aes_repl = 1;      // tables and replicas in LDS (FCGPU_ESPAES_TABLES / _REPLICAS)
     uint32_t aes_tile = 0;                    // packets per tile; 0: by the batch's size (FCGPU_ESPAES_TILE)
     uint8_t *aes_status = nullptr;            // [max_batch] FCGPU_ESP_* of the last batch
@@ -449,8 +454,9 @@ hipError_t launch_espauth(const fcgpu_ctx *c, const uint8_t *arena, const uint32
 
 // ---- fcgpu_espaes_api.hip ---------------------------------------------------
 void espaes_free(fcgpu_ctx *c);
-// the ESP decryption post-pass (k_espaes) over one batch: it WRITES the
-// frames of `arena` in place and c->aes_status
+// the ESP decryption (k_espaes) or, by c->aes_mode, encryption (k_espenc)
+// post-pass over one batch: it WRITES the frames of `arena` in place and
+// c->aes_status
 hipError_t launch_espaes(const fcgpu_ctx *c, const uint8_t *arena, const uint32_t *desc, const uint16_t *verdict,
                          const fcgpu_anno *anno, uint32_t n, hipStream_t s);
 

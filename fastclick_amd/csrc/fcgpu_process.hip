@@ -135,8 +135,11 @@ int process_one(fcgpu_ctx *c, const uint8_t *d_arena, const uint32_t *d_desc, ui
                             timed ? ev[0].b : nullptr, c->jit_src.empty() ? nullptr : c));
     HIPCHK(c, hipGetLastError());
     if (c->agc_tab) HIPCHK(c, launch_aggcount(c, a.verdict, a.hash, a.anno, n, s));
-    if (c->aes_sa) HIPCHK(c, launch_espaes(c, d_arena, d_desc, a.verdict, a.anno, n, s));   // in front: espauth reads plaintext
+    // decryption in front: espauth reads plaintext; encryption behind: authenticate, then encrypt (ipsec-router.click)
+    const bool enc = c->aes_sa && c->aes_mode == FCGPU_ESPAES_ENCRYPT;
+    if (c->aes_sa && !enc) HIPCHK(c, launch_espaes(c, d_arena, d_desc, a.verdict, a.anno, n, s));
     if (c->esp_sa) HIPCHK(c, launch_espauth(c, d_arena, d_desc, a.verdict, a.anno, n, s));
+    if (enc) HIPCHK(c, launch_espaes(c, d_arena, d_desc, a.verdict, a.anno, n, s));
     if (a.fl.slots) {   // the batch's new flows get their IDs (fcgpu_flow.hh)
         HIPCHK(c, flow_pass(c, a.fl, n, s));
         if (cross) {

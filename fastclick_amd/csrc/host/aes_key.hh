@@ -1,5 +1,6 @@
-// aes_key.hh -- the security-association table of the ESP decryption stage
-// (fcgpu_espaes_set_sas) and the AES-128 inverse tables, built on the host.
+// aes_key.hh -- the security-association table of the ESP decryption and
+// encryption stage (fcgpu_espaes_set_sas) and the AES-128 tables, built on the
+// host.
 //
 // Semantics: IPsecAES(0) (elements/ipsec/aes.cc:69-138, decrypt branch)
 // decrypts 16-byte blocks with standard AES-128 (FIPS 197). The kernel runs
@@ -24,8 +25,19 @@
 // Device image: an array sorted by SPI of 192-byte records
 // {spi, rk[44], pad[3]}: rk[0..3] = w[40..43], rk[4r..4r+3] =
 // InvMixColumns(w[40-4r..43-4r]) for r = 1..9, rk[40..43] = w[0..3]. SPI 0 and
-// duplicate SPIs are refused, as are more than kMaxSas. No HIP here: the
-// library and CPU programs share this file.
+// duplicate SPIs are refused, as are more than kMaxSas.
+//
+// Encryption, IPsecAES(1) (aes.cc:115-133): the cipher of FIPS
+// 197 5.1 in the same byte order, with one forward table
+//   Te0[x] = 02.s | s << 8 | s << 16 | 03.s << 24, s = Sbox[x],
+// row 0's contribution to MixColumns(SubBytes(.)); rows 1..3 take Te0 rotated
+// left by 8, 16, 24 bits. Round r = 1..9 of column c is
+//   t[c] = Te0[s[c] & ff] ^ rol8(Te0[s[c+1] >> 8 & ff]) ^ rol16(Te0[s[c+2] >> 16 & ff])
+//          ^ rol24(Te0[s[c+3] >> 24]) ^ rk[4r + c]        (columns mod 4)
+// (ShiftRows in the choice of source columns); the last round takes the S-box
+// byte from byte 1 of the same word. The encryption records have the shape of
+// the decryption ones, rk[4r + c] = w[4r + c], in the same SPI order.
+// No HIP here: the library and CPU programs share this file.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -49,6 +61,7 @@ static_assert(sizeof(SaDev) == 192, "the kernel reads 48 words per SA");
 struct Tables {
     uint8_t sbox[256], isbox[256];
     uint32_t td0[256];
+    uint32_t te0[256];
 };
 
 constexpr uint8_t xtime(uint8_t a) { return (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1b : 0)); }
@@ -82,6 +95,8 @@ constexpr Tables make_tables() {
         const uint8_t s = t.isbox[v];
         t.td0[v] = (uint32_t)gmul(s, 0x0e) | (uint32_t)gmul(s, 0x09) << 8 | (uint32_t)gmul(s, 0x0d) << 16 |
                    (uint32_t)gmul(s, 0x0b) << 24;
+        const uint8_t f = t.sbox[v];
+        t.te0[v] = (uint32_t)gmul(f, 0x02) | (uint32_t)f << 8 | (uint32_t)f << 16 | (uint32_t)gmul(f, 0x03) << 24;
     }
     return t;
 }
@@ -148,21 +163,63 @@ inline void decrypt_block(const uint32_t rk[kRkWords], const uint8_t in[16], uin
     }
 }
 
-// The device image of n SAs, sorted by SPI. Returns FCGPU_OK or FCGPU_EINVAL
-// with `err` set; `im` is written only on success.
-inline int build(const fcgpu_espaes_sa *sa, uint32_t n, std::vector<SaDev> &im, std::string &err) {
+// The encryption schedule: the 44 words w[] as little-endian columns.
+inline void enc_round_keys(const uint8_t key[16], uint32_t rk[kRkWords]) {
+    uint8_t w[176];
+    expand_key(key, w);
+    for (uint32_t k = 0; k < kRkWords; ++k) rk[k] = le32(w + 4 * k);
+}
+
+// One block through the encryption round keys and Te0: what a lane quad of
+// k_espenc computes, column c in lane c.
+inline void encrypt_block(const uint32_t rk[kRkWords], const uint8_t in[16], uint8_t out[16]) {
+    uint32_t s[4], t[4];
+    for (int c = 0; c < 4; ++c) s[c] = le32(in + 4 * c) ^ rk[c];
+    for (int r = 1; r < 10; ++r) {
+        for (int c = 0; c < 4; ++c)
+            t[c] = kTables.te0[s[c] & 0xff] ^ rol(kTables.te0[(s[(c + 1) & 3] >> 8) & 0xff], 8) ^
+                   rol(kTables.te0[(s[(c + 2) & 3] >> 16) & 0xff], 16) ^ rol(kTables.te0[s[(c + 3) & 3] >> 24], 24) ^
+                   rk[4 * r + c];
+        memcpy(s, t, sizeof s);
+    }
+    for (int c = 0; c < 4; ++c) {           // the S-box: bytes 1 and 2 of a Te0 word
+        const uint32_t v = (((kTables.te0[s[c] & 0xff] >> 8) & 0xffu) | (kTables.te0[(s[(c + 1) & 3] >> 8) & 0xff] & 0xff00u) |
+                            (kTables.te0[(s[(c + 2) & 3] >> 16) & 0xff] & 0xff0000u) |
+                            ((kTables.te0[s[(c + 3) & 3] >> 24] << 8) & 0xff000000u)) ^ rk[40 + c];
+        for (int b = 0; b < 4; ++b) out[4 * c + b] = (uint8_t)(v >> (8 * b));
+    }
+}
+
+// The device images of n SAs, sorted by SPI: `im` for decryption and, where
+// `enc` is given, the encryption records in the same order. Returns FCGPU_OK
+// or FCGPU_EINVAL with `err` set; the images are written only on success.
+inline int build(const fcgpu_espaes_sa *sa, uint32_t n, std::vector<SaDev> &im, std::string &err,
+                 std::vector<SaDev> *enc = nullptr) {
     if (n > kMaxSas) { err = "more than 65536 SAs"; return FCGPU_EINVAL; }
-    std::vector<SaDev> t(n);
+    std::vector<uint32_t> order(n);
     for (uint32_t k = 0; k < n; ++k) {
         if (sa[k].spi == 0) { err = "SA " + std::to_string(k) + ": SPI 0"; return FCGPU_EINVAL; }
-        t[k].spi = sa[k].spi;
-        memset(t[k].pad, 0, sizeof t[k].pad);
-        dec_round_keys(sa[k].enc_key, t[k].rk);
+        order[k] = k;
     }
-    std::sort(t.begin(), t.end(), [](const SaDev &x, const SaDev &y) { return x.spi < y.spi; });
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return sa[x].spi < sa[y].spi; });
     for (uint32_t k = 1; k < n; ++k)
-        if (t[k].spi == t[k - 1].spi) { err = "duplicate SPI " + std::to_string(t[k].spi); return FCGPU_EINVAL; }
+        if (sa[order[k]].spi == sa[order[k - 1]].spi) {
+            err = "duplicate SPI " + std::to_string(sa[order[k]].spi);
+            return FCGPU_EINVAL;
+        }
+    std::vector<SaDev> t(n), e(enc ? n : 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const fcgpu_espaes_sa &src = sa[order[k]];
+        t[k].spi = src.spi;
+        memset(t[k].pad, 0, sizeof t[k].pad);
+        dec_round_keys(src.enc_key, t[k].rk);
+        if (enc) {
+            e[k] = t[k];
+            enc_round_keys(src.enc_key, e[k].rk);
+        }
+    }
     im.swap(t);
+    if (enc) enc->swap(e);
     return FCGPU_OK;
 }
 

@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FCGPU_ABI_VERSION 31
+#define FCGPU_ABI_VERSION 32
 
 #define FCGPU_OK          0
 #define FCGPU_EINVAL     -1   /* bad argument / configuration            */
@@ -836,11 +836,22 @@ int  fcgpu_aggcount_read(fcgpu_ctx *ctx, fcgpu_aggcount_rec *h_out, uint32_t max
  *     or FCGPU_ESP_BAD; the record's icv holds the computed 12 bytes;
  *   - FCGPU_ESP_COMPUTE: icv = the first 12 bytes of HMAC-SHA1(auth_key,
  *     frame[e0, end)), the bytes put(12) would append; FCGPU_ESP_OK.
- * Frames are never written; verdict, hash, the partition and the counters are
- * untouched. Out of scope: IPsecESPUnencap, anti-replay and the element
+ *   - FCGPU_ESP_SEAL: the outbound IPsecAuthHMACSHA1(0) for a frame that
+ *     already holds room for the digest. Selection and statuses are VERIFY's
+ *     (elen < 28: FCGPU_ESP_SHORT); the digest is HMAC-SHA1(auth_key,
+ *     frame[e0, end - 12)); its first 12 bytes are WRITTEN to frame[end - 12,
+ *     end) and the record holds FCGPU_ESP_OK and the same 12 bytes. Those 12
+ *     bytes of OK packets are written and no other byte, by naturally aligned
+ *     byte, short or dword stores chosen by the address's low bits (no
+ *     read-modify-write of a shared word); nothing past `end` is read beyond
+ *     the 16-byte slack. While SEAL is configured fcgpu_process writes
+ *     d_arena.
+ * VERIFY and COMPUTE never write frames; verdict, hash, the partition and the
+ * counters are untouched. Out of scope: IPsecESPUnencap, anti-replay and the element
  * keyword. With the decryption stage below installed as well, k_espaes runs
  * in front of this stage on the same stream, so the digest is taken over the
- * decrypted bytes, as in the reference's chain.
+ * decrypted bytes, as in the reference's chain; with that stage in its
+ * encryption mode this stage runs first (authenticate, then encrypt).
  * The stage is a post-pass kernel behind k_rx on the batch's stream (DESIGN.md
  * 3.10). Its records are one context-owned array of max_batch entries holding
  * the last fcgpu_process batch; where the caller leaves fcgpu_out.verdict or
@@ -852,6 +863,7 @@ int  fcgpu_aggcount_read(fcgpu_ctx *ctx, fcgpu_aggcount_rec *h_out, uint32_t max
  * fcgpu_span_submit_block return FCGPU_EINVAL. */
 #define FCGPU_ESP_VERIFY  0u
 #define FCGPU_ESP_COMPUTE 1u
+#define FCGPU_ESP_SEAL    2u
 #define FCGPU_ESP_NOT_ESP 0
 #define FCGPU_ESP_OK      1
 #define FCGPU_ESP_BAD     2
@@ -863,7 +875,7 @@ typedef struct fcgpu_esp_sa {
     uint8_t auth_key[16];
 } fcgpu_esp_sa;
 typedef struct fcgpu_espauth_config {
-    uint32_t mode;          /* FCGPU_ESP_VERIFY | FCGPU_ESP_COMPUTE */
+    uint32_t mode;          /* FCGPU_ESP_VERIFY | FCGPU_ESP_COMPUTE | FCGPU_ESP_SEAL */
 } fcgpu_espauth_config;
 typedef struct fcgpu_esp_rec {
     uint8_t status;         /* FCGPU_ESP_* */
@@ -877,7 +889,8 @@ typedef struct fcgpu_espauth_stat {
  * disables the stage and frees it. FCGPU_EINVAL: SPI 0, a duplicate SPI, more
  * than FCGPU_ESPAUTH_MAX_SAS. Synchronises the device. */
 int  fcgpu_espauth_set_sas(fcgpu_ctx *ctx, const fcgpu_esp_sa *sas, uint32_t n);
-/* The mode of the batches submitted after this call (default VERIFY). */
+/* The mode of the batches submitted after this call (default VERIFY).
+ * FCGPU_EINVAL: a mode above FCGPU_ESP_SEAL. */
 int  fcgpu_espauth_configure(fcgpu_ctx *ctx, const fcgpu_espauth_config *cfg);
 /* Device pointer to the records, [max_batch]: entry i is packet i of the last
  * fcgpu_process batch, ordered behind it on its stream. NULL while disabled. */
@@ -921,22 +934,52 @@ int  fcgpu_espauth_reset(fcgpu_ctx *ctx);
  * aggregate counter, k_espaes, k_espauth, the flow pass.
  * Served by fcgpu_process; while SAs are installed fcgpu_process_jobs,
  * fcgpu_process_host, fcgpu_process_counted, fcgpu_process_mbufs,
- * fcgpu_span_submit and fcgpu_span_submit_block return FCGPU_EINVAL. Out of
- * scope: IPsecAES(1) (encryption), IPsecESPUnencap, anti-replay, the element
+ * fcgpu_span_submit and fcgpu_span_submit_block return FCGPU_EINVAL.
+ *
+ * FCGPU_ESPAES_ENCRYPT (fcgpu_espaes_configure) is IPsecAES(1), the encrypt
+ * branch of the same element (aes.cc:115-133), the last transform of the
+ * outbound chain rt[1] -> IPsecESPEncap -> IPsecAuthHMACSHA1(0) -> IPsecAES(1)
+ * -> IPsecEncap(50). Packet selection, e0, end, elen, plen, the statuses, the
+ * region rule (plen % 16 == 8 extends the region over the first 8 digest
+ * bytes) and nblk are exactly the rules above. Block i is P_i = frame[e0 + 16
+ * + 16 i, + 16); it becomes C_i = AES128-encrypt(enc_key, P_i') where P_i' is
+ * P_i with its FIRST 8 BYTES ONLY XORed with IV = frame[e0 + 8, e0 + 16) for
+ * i = 0 and with C_{i-1}[0, 8) otherwise. In place: exactly the 16 * nblk
+ * bytes of every OK packet are written and nothing else; the IV is read and
+ * never written; fcgpu_espaes_stat.blocks counts blocks encrypted. The status
+ * array, the statistics, the NULL-output scratch and the refusals of the
+ * other entry points are those of decryption. A packet is a serial chain of
+ * nblk dependent block encryptions (k_espenc).
+ * Launch order with the encryption mode: k_rx, the aggregate counter,
+ * k_espauth, k_espenc, the flow pass -- the reference's
+ * authenticate-then-encrypt order, so one fcgpu_process call with
+ * FCGPU_ESP_SEAL and FCGPU_ESPAES_ENCRYPT turns an IPsecESPEncap-shaped frame
+ * (SPI, sequence number, IV, padded payload, 12 bytes of room) into the wire
+ * packet's ESP part. Either stage alone keeps working.
+ * Out of scope: IPsecESPEncap itself (frame growth, random IVs, the replay
+ * counter), IPsecEncap(50), IPsecESPUnencap, anti-replay, the element
  * keyword. */
 #define FCGPU_ESP_UNALIGNED 5
 #define FCGPU_ESPAES_MAX_SAS 65536u
+#define FCGPU_ESPAES_DECRYPT 0u
+#define FCGPU_ESPAES_ENCRYPT 1u
 typedef struct fcgpu_espaes_sa {
     uint32_t spi;           /* host order; never 0 */
     uint8_t enc_key[16];
 } fcgpu_espaes_sa;
+typedef struct fcgpu_espaes_config {
+    uint32_t mode;          /* FCGPU_ESPAES_DECRYPT | FCGPU_ESPAES_ENCRYPT */
+} fcgpu_espaes_config;
 typedef struct fcgpu_espaes_stat {
-    uint64_t ok, no_sa, too_short, unaligned, not_esp, blocks;   /* blocks: 16-byte blocks decrypted */
+    uint64_t ok, no_sa, too_short, unaligned, not_esp, blocks;   /* blocks: 16-byte blocks decrypted / encrypted */
 } fcgpu_espaes_stat;
-/* Replaces the SA table (the statistics restart); n == 0 disables the stage
- * and frees it. FCGPU_EINVAL: SPI 0, a duplicate SPI, more than
+/* Replaces the SA table (the statistics restart, the mode stays); n == 0
+ * disables the stage and frees it. FCGPU_EINVAL: SPI 0, a duplicate SPI, more than
  * FCGPU_ESPAES_MAX_SAS. Synchronises the device. */
 int  fcgpu_espaes_set_sas(fcgpu_ctx *ctx, const fcgpu_espaes_sa *sas, uint32_t n);
+/* The mode of the batches submitted after this call (default DECRYPT); it may
+ * be called with no table installed. FCGPU_EINVAL: any other mode. */
+int  fcgpu_espaes_configure(fcgpu_ctx *ctx, const fcgpu_espaes_config *cfg);
 /* Device pointer to the status bytes (FCGPU_ESP_*), [max_batch]: entry i is
  * packet i of the last fcgpu_process batch. NULL while disabled. */
 int  fcgpu_espaes_status(fcgpu_ctx *ctx, const uint8_t **d_status);

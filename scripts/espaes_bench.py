@@ -5,7 +5,7 @@ fcgpu_espaes_set_sas) on ESP/IPv4 frames with a seeded random payload:
 32 and 90 blocks), four SAs, checksum, FLOWID hash, tile partition, 8 rotating
 device copies. Every frame's IP length is cut so that plen % 8 == 0.
 
-    python scripts/espaes_bench.py [--steps 64] [--repeat 3] [--n 1048576] [--ab]
+    python scripts/espaes_bench.py [--steps 64] [--repeat 3] [--n 1048576] [--ab] [--mode decrypt|encrypt]
 
 Per row one JSON line: step_us = device time per fcgpu_process call (events
 around `steps` calls, median of `repeat` rounds), k_rx_us = k_rx alone (every
@@ -15,7 +15,14 @@ stage), `auth` (k_espauth alone, the yardstick of the same session) and
 of it, gbps = decrypted bytes per second of it. --ab adds, for the 1500-B
 batch, one row per table layout: t<tables>r<replicas> (FCGPU_ESPAES_TABLES,
 FCGPU_ESPAES_REPLICAS). The stage decrypts the rotating copies in place again
-and again: the work does not depend on the bytes."""
+and again: the work does not depend on the bytes.
+
+--mode encrypt takes the outbound rows on the same batches:
+`enc` (k_espenc, fcgpu_espaes_configure(ENCRYPT)), `seal` (k_espauth in
+FCGPU_ESP_SEAL), `both` (SEAL then ENCRYPT in one call) and `aes` (k_espaes,
+decryption, the yardstick of the same session). --ab then adds, for the IMIX
+batch, k_espenc sorted by block count against arrival order
+(FCGPU_ESPENC_ORDER), two alternating rounds."""
 import argparse
 import json
 import os
@@ -50,13 +57,15 @@ def batch_for(flen, seed):
     return b, int((((flen - 62) // 8 * 8 + 8) // 16).sum())
 
 
-def time_row(name, b, blocks, steps, repeat, aes=False, auth=False):
+def time_row(name, b, blocks, steps, repeat, aes=False, auth=False, outbound=False):
     n = b.n
     ctx = N.Context(0, n, N.make_cfg(offset=14, checksum=True, hash_mode=N.HASH_FLOWID, nports=NPORTS))
     if aes:
         ctx.espaes_set_sas(SAS)
+        ctx.espaes_configure(N.ESPAES_ENCRYPT if outbound else N.ESPAES_DECRYPT)
     if auth:
         ctx.espauth_set_sas(SAS)
+        ctx.espauth_configure(N.ESP_SEAL if outbound else N.ESP_VERIFY)
     db = DeviceBatch.upload(b, device="cuda:0")
     bufs = [(db.arena, db.desc)] + [(db.arena.clone(), db.desc.clone()) for _ in range(7)]
     outs = DeviceOutputs(n, NPORTS, device="cuda:0", anno=True, tile_perm=True, partition=N.PART_TILE)
@@ -94,6 +103,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--mode", choices=["decrypt", "encrypt"], default="decrypt")
     args = ap.parse_args()
     rng = np.random.default_rng(3)
     shapes = {"64": np.full(args.n, 64), "1500": np.full(max(args.n * 64 // 1536, 1), 1500),
@@ -101,6 +111,18 @@ def main():
     for name, flen in shapes.items():
         b, blocks = batch_for(flen, seed=len(name))
         time_row(f"off/{name}", b, blocks, args.steps, args.repeat)
+        if args.mode == "encrypt":
+            time_row(f"enc/{name}", b, blocks, args.steps, args.repeat, aes=True, outbound=True)
+            time_row(f"seal/{name}", b, blocks, args.steps, args.repeat, auth=True, outbound=True)
+            time_row(f"both/{name}", b, blocks, args.steps, args.repeat, aes=True, auth=True, outbound=True)
+            time_row(f"aes/{name}", b, blocks, args.steps, args.repeat, aes=True)
+            if args.ab and name == "imix":
+                for rnd in range(2):
+                    for o in "10":
+                        os.environ["FCGPU_ESPENC_ORDER"] = o
+                        time_row(f"order{o}.{rnd}/{name}", b, blocks, args.steps, args.repeat, aes=True, outbound=True)
+                del os.environ["FCGPU_ESPENC_ORDER"]
+            continue
         time_row(f"aes/{name}", b, blocks, args.steps, args.repeat, aes=True)
         time_row(f"auth/{name}", b, blocks, args.steps, args.repeat, auth=True)
         time_row(f"both/{name}", b, blocks, args.steps, args.repeat, aes=True, auth=True)

@@ -199,6 +199,7 @@ int fcgpu_espauth_records(fcgpu_ctx *, const fcgpu_esp_rec **d) { *d = nullptr; 
 int fcgpu_espauth_stats(fcgpu_ctx *, fcgpu_espauth_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
 int fcgpu_espauth_reset(fcgpu_ctx *) { return FCGPU_OK; }
 int fcgpu_espaes_set_sas(fcgpu_ctx *, const fcgpu_espaes_sa *, uint32_t) { return FCGPU_OK; }
+int fcgpu_espaes_configure(fcgpu_ctx *, const fcgpu_espaes_config *) { return FCGPU_OK; }
 int fcgpu_espaes_status(fcgpu_ctx *, const uint8_t **d) { *d = nullptr; return FCGPU_OK; }
 int fcgpu_espaes_stats(fcgpu_ctx *, fcgpu_espaes_stat *st) { memset(st, 0, sizeof *st); return FCGPU_OK; }
 int fcgpu_espaes_reset(fcgpu_ctx *) { return FCGPU_OK; }
